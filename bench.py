@@ -2,7 +2,9 @@
 
 One JSON line on rank 0 (contract in the task statement).  A "step" = noise -> q-sample -> UNet forward -> MSE ->
 backward -> (gradient all-reduce) -> clip_grad_norm_ -> AdamW on one synthetic batch already resident in HBM.
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+--dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy; the inputs (weights, volume, noise and
+timestep draws) are seeded, so two builds run with the same arguments can be compared output for output.
 N > 1: one rank per GPU over RCCL -- either started by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
 (RANK / WORLD_SIZE in the environment) or, without a launcher, by bench.py itself as a child process.
 """
@@ -143,6 +145,29 @@ def step_breakdown(tr, x0, noise, t):
     return out
 
 
+DUMP_SAMPLE = 1 << 22  # elements of the parameter / gradient samples: 2 x 16 MB
+
+
+def dump_outputs(out_dir, net, tr, loss):
+    """What the last timed step computed, as float32 .npy files in out_dir:
+    loss.npy            [1]  the loss the step returned;
+    params_sample.npy   [m]  the updated parameters, grads_sample.npy [m] the gradients of that step: both the same fixed sample (numpy
+                        default_rng(0), sorted, without replacement) of m = min(DUMP_SAMPLE, numel) positions of the concatenation of
+                        the model's parameters in named_parameters() order, which does not depend on the library's arena layout."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    a = tr.arena
+    names = [n for n, _ in net.named_parameters()]
+    params = torch.cat([a.view(n).reshape(-1) for n in names])
+    grads = torch.cat([a.gview(n).reshape(-1) for n in names])
+    m = min(DUMP_SAMPLE, params.numel())
+    idx = np.sort(np.random.default_rng(0).choice(params.numel(), size=m, replace=False))
+    idx = torch.from_numpy(idx).to(params.device)
+    arrays = {"loss": loss.detach().reshape(-1), "params_sample": params[idx], "grads_sample": grads[idx]}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -153,7 +178,10 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--roofline-only", action="store_true", help="only time the dominant kernels (for rocprofv3 cross-checks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, parameters and gradients (sampled) to DIR")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.roofline_only:
         torch.cuda.set_device(0)
@@ -241,6 +269,9 @@ def main():
     # A step that computes garbage is not a measurement (and NaN operands even run FASTER: less MFMA power, higher clocks).
     if not bool(torch.isfinite(loss.detach().float()).all()) or not bool(torch.isfinite(tr.arena.data).all()):
         raise RuntimeError(f"bench: non-finite loss / parameters after the timed steps (loss = {float(loss)}): refusing to report a number")
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, net, tr, loss)  # before step_breakdown below, which runs one more (eager) step
 
     if rank == 0:
         # algorithmic flops of one step of this model (engine counters: 2*MACs, bwd = dgrad + wgrad)
