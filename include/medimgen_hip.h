@@ -257,6 +257,32 @@ int mi_ls_gan_loss(const void* logits, int cs, int64_t nvox, float target, float
 int mi_bn_running_update(const float* mean_rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, int C, float eps,
                          float momentum, int64_t count, hipStream_t stream);
 
+/* ---- LPIPS-VGG perceptual loss of the generator step (train_autoencoder.py:416 `perceptual_loss(recon, images) * perc_weight`, :601
+ * `PerceptualLoss(**perceptual_params)`; third-party `generative` / `lpips` classes: PARITY UNPINNED).  The VGG16 3x3 convs run on 2-D
+ * conv plans (kernel (1,3,3), padding (0,1,1)) with forward and data gradient only; slices are [S][A][B][C] bf16 (the plans' D = 1).
+ * Fake 3-D: slice i of spatial `axis` (0 = D, 1 = H, 2 = W) is (n, l) = (i / L, i % L) with L the axis' extent, its pixel axes are the
+ * two other spatial axes in order.  Indices are device int32 [S]; an index outside [0, N*L) reads a zero slice and scatters nothing. */
+/* out [S][A][B][8] = ((x - shift_c) / scale_c for c < 3, 0 for c >= 3); x: [N][D][H][W][x_cstride] with C in {1, 3} channels (one
+ * channel broadcasts to three); shift / scale: fp32 [3] (the scaling layer's buffers) */
+int mi_perc_gather(const void* x, int x_cstride, int C, int N, int D, int H, int W, int axis, const int* idx, int S, const float* shift,
+                   const float* scale, void* out, hipStream_t stream);
+/* the adjoint: dx[voxel of slice s, pixel (a, b)] += sum_c dslices[s][a][b][c] / scale_c (c < 3; C = 3: per channel).  The indices of
+ * ONE call must be distinct (each voxel belongs to at most one slice: no atomics) */
+int mi_perc_scatter_add(const void* dslices, int axis, const int* idx, int S, int N, int D, int H, int W, int C, const float* scale, void* dx,
+                        int dx_cstride, hipStream_t stream);
+/* out [Cout][Cin_pad][taps] fp32 = w [Cout][Cin][taps] with zero channels Cin .. Cin_pad-1 */
+int mi_pad_cin_f32(const float* w, float* out, int Cout, int Cin, int Cin_pad, int taps, hipStream_t stream);
+/* x [N][H][W][C] bf16 rectified IN PLACE; pooled (may be NULL) [N][H/2][W/2][C] = 2x2 / stride-2 max-pool of the rectified x */
+int mi_relu_maxpool2_fwd(void* x, void* pooled, int N, int H, int W, int C, hipStream_t stream);
+/* dx = (dadd + route(dpooled)) * (a > 0), a = the rectified tensor; the pooled gradient goes to the first maximum of its window in scan
+ * order (torch's max_pool2d); dpooled / dadd may be NULL (not both); dx may alias dadd */
+int mi_relu_maxpool2_bwd(const void* a, const void* dpooled, const void* dadd, void* dx, int N, int H, int W, int C, hipStream_t stream);
+/* one LPIPS level: f0 / f1 [S][P][C] bf16 (C in {64, 128, 256, 512}), w fp32 [C] (lin head, no bias);
+ * *loss += weight / (S P) * sum_{s,p} sum_c w_c (f0/(|f0|+eps) - f1/(|f1|+eps))_c^2 (ACCUMULATED);
+ * df0 (may be NULL) = the gradient of that term w.r.t. f0 */
+int mi_lpips_head(const void* f0, const void* f1, const float* w, int S, int64_t P, int C, float weight, float eps, float* loss, void* df0,
+                  hipStream_t stream);
+
 /* ---- train-step glue: scheduler.add_noise (T-LDM:160), F.mse_loss (+backward) (T-LDM:169, T-DDPM:192) ------------------- */
 int mi_qsample(const float* x0, const float* noise, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod,
                const int64_t* timesteps, const float* cond, int cond_channels, void* out, float* velocity, int N, int C, int64_t V,

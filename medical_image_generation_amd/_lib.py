@@ -86,6 +86,12 @@ _SIGS = {
     "mi_col2im3d": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "mi_disc_pack_weights": [_p, _p, _p, _i, _i, _i, _i, _p],
     "mi_disc_wgrad_unpack": [_p, _p, _i, _i, _i, _p],
+    "mi_perc_gather": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p],
+    "mi_perc_scatter_add": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p],
+    "mi_pad_cin_f32": [_p, _p, _i, _i, _i, _i, _p],
+    "mi_relu_maxpool2_fwd": [_p, _p, _i, _i, _i, _i, _p],
+    "mi_relu_maxpool2_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
+    "mi_lpips_head": [_p, _p, _p, _i, _l, _i, _f, _f, _p, _p, _p],
     "mi_leaky_relu_fwd": [_p, _p, _l, _f, _p],
     "mi_leaky_relu_bwd": [_p, _p, _p, _l, _f, _p],
     "mi_ls_gan_loss": [_p, _i, _l, _f, _f, _p, _p, _f, _p],
@@ -109,7 +115,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 def exported_symbols() -> list[str]:

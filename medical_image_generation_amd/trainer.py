@@ -8,7 +8,7 @@ optimizer is one fused launch over the flat parameter arena, and the whole step 
 (`capture=True`) and replayed, which removes the Python / launch overhead of ~600 kernel launches.
 
 `AETrainer` is the same thing for the generator step of train_autoencoder.AutoEncoder.train_one_epoch (T-AE:406-435):
-encode -> sample -> decode -> L1 + kl_weight * KL (+ the caller's perceptual / adversarial terms through `extra_loss`, evaluated by
+encode -> sample -> decode -> L1 + kl_weight * KL (+ the native LPIPS-VGG term, `perceptual=`; + the caller's terms through `extra_loss`, evaluated by
 torch autograd on the reconstruction: those networks are third-party torch modules) -> backward -> Adam.
 
 Data parallelism: one process per GPU; the trainable prefix of the flat gradient arena is all-reduced
@@ -386,17 +386,68 @@ class AETrainer(_ArenaTrainer):
     (reconstruction fp32 NCDHW with requires_grad, images) -> scalar torch loss; it runs under torch autograd on the GPU and its
     gradient with respect to the reconstruction joins the L1 gradient before the HIP backward.  The networks inside it
     (`generative`'s PatchDiscriminator / PerceptualLoss with downloaded weights) stay the user's torch modules -- they are not
-    rebuilt here.  `reconstruction` (fp32 NCDHW, detached) holds the last step's output for the caller's discriminator step
+    rebuilt here.
+
+    perceptual: a perceptual.PerceptualLoss (LPIPS-VGG with the user's weights) run natively inside the step: perc_weight *
+    LPIPS(recon, images) joins `loss` (and is kept in the device scalar `perc_loss`), its gradient joins the L1 gradient on the HIP
+    path, and capture() / step_graph() include it.  The fake-3D slice indices are drawn on the CPU generator before every step /
+    replay (`perc_indices=` pins them).  Both terms may be set; they add.  `reconstruction` (fp32 NCDHW, detached) holds the last step's output for the caller's discriminator step
     (T-AE:371-397), which is plain torch on the caller's side."""
 
     def __init__(self, model, lr=5e-5, optimizer="Adam", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 kl_weight=1e-7, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, extra_loss=None, overlap=None):
+                 kl_weight=1e-7, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, extra_loss=None, overlap=None,
+                 perceptual=None, perc_weight=0.125):
         super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
                          grad_accumulate_step, overlap)
         self.kl_weight = float(kl_weight)
         self.extra_loss = extra_loss
         self.reconstruction = None
         self.extra_loss_value = None
+        # native perceptual term (perceptual.PerceptualLoss): perc_weight * LPIPS(recon, images), T-AE:416; the slice indices of a
+        # fake-3D loss live in static device buffers refilled before every step / replay (never drawn inside a graph)
+        self.perceptual = perceptual
+        self.perc_weight = float(perc_weight)
+        self.perc_loss = torch.zeros(1, dtype=F32, device=self.device)  # perc_weight * perceptual loss of the last step
+        self._perc_idx = None
+        if perceptual is not None:
+            from .perceptual import PerceptualLoss
+            if not isinstance(perceptual, PerceptualLoss):
+                raise TypeError("perceptual must be a medical_image_generation_amd.perceptual.PerceptualLoss (torch modules go in extra_loss)")
+            perceptual.to(self.device)
+
+    def _fill_perc_indices(self, shape, indices=None):
+        """Copy the slice indices of the next step into the static buffers: `indices` (three index tensors) or a fresh draw
+        (PerceptualLoss.draw_indices on the CPU generator, as upstream draws in every forward)."""
+        if self.perceptual is None:
+            return
+        if indices is None:
+            indices = self.perceptual.draw_indices(tuple(shape))
+        if not indices:
+            return
+        bufs = self._perc_idx
+        if bufs is None or [b.numel() for b in bufs] != [i.numel() for i in indices]:
+            if self._graph:
+                raise ValueError("the slice counts differ from the captured step's")
+            bufs = self._perc_idx = [torch.empty(i.numel(), dtype=torch.int32, device=self.device) for i in indices]
+        for b, i in zip(bufs, indices):
+            b.copy_(i.reshape(-1))
+
+    def step(self, images, eps, last_in_epoch=False, perc_indices=None):
+        """perc_indices: the three slice-index tensors of the perceptual term's fake-3D axes (default: a fresh draw)."""
+        self._fill_perc_indices(images.shape, perc_indices)
+        return super().step(images, eps, last_in_epoch=last_in_epoch)
+
+    def capture(self, images, eps, warmup=2, perc_indices=None):
+        self._fill_perc_indices(images.shape, perc_indices)
+        super().capture(images, eps, warmup=warmup)
+        if self.perceptual is not None:
+            self._pinned.append((dict(self.perceptual._plans), self.perceptual._w1, self._perc_idx))
+
+    def step_graph(self, images=None, eps=None, perc_indices=None):
+        """Replay; the perceptual term's slice indices are refilled first (fresh draw unless given) -- every replay uses new ones."""
+        if self.perceptual is not None and self._graph:
+            self._fill_perc_indices(self._static[0].shape, perc_indices)
+        return super().step_graph(images, eps)
 
     def _forward(self, images, eps):
         m, a = self.model, self.arena
@@ -426,6 +477,10 @@ class AETrainer(_ArenaTrainer):
         recon = m._decode_run(ctx, z, True)
         drecon = torch.empty_like(recon)
         call("mi_l1_fwd_bwd", ptr(recon), ptr(images), ptr(drecon), ptr(self.loss), n, recon.shape[-1], v, 1)
+        if self.perceptual is not None:
+            self.perc_loss.zero_()
+            self.perceptual.hip(recon, x_cl, self._perc_idx, self.perc_loss, self.perc_weight, grad=drecon)  # gradient added into drecon
+            ops.add_f32_(self.loss.view(1, 1), self.perc_loss.view(1, 1))
         if self.extra_loss is not None:
             rec = ops.to_channels_first(recon, len(sp)).requires_grad_(True)
             with torch.enable_grad():
@@ -448,8 +503,8 @@ class AEGANTrainer(AETrainer):
 
     `discriminator`: medical_image_generation_amd.discriminator.PatchDiscriminator; LS = PatchAdversarialLoss("least_squares").
     step(images, eps) runs both (the reference's order: generator, then discriminator on the same reconstruction); `adversarial`
-    switches the adversarial term and the discriminator step on (epoch >= autoencoder_warm_up_epochs).  The perceptual term needs
-    downloaded weights and stays the caller's `extra_loss`.  capture() / step_graph() replay generator and discriminator graphs."""
+    switches the adversarial term and the discriminator step on (epoch >= autoencoder_warm_up_epochs).  The perceptual term is
+    AETrainer's `perceptual=` (native) or the caller's `extra_loss`.  capture() / step_graph() replay generator and discriminator graphs."""
 
     def __init__(self, model, discriminator, adv_weight=0.01, d_lr=5e-5, adversarial=True, **kw):
         super().__init__(model, **kw)
@@ -515,15 +570,15 @@ class AEGANTrainer(AETrainer):
         call("mi_adam_step", ptr(a.data), ptr(a.grad), ptr(self.d_exp_avg), ptr(self.d_exp_avg_sq), n, self.d_lr, self.betas[0], self.betas[1],
              self.eps, 0.0, 0, ptr(self.d_sumsq) if clip else None, float(self.max_grad_norm or 0.0), 1.0 / self.world, ptr(self.d_step_count))
 
-    def step(self, images, eps, last_in_epoch=False):
-        loss = super().step(images, eps)
+    def step(self, images, eps, last_in_epoch=False, perc_indices=None):
+        loss = super().step(images, eps, perc_indices=perc_indices)
         if self.adversarial:
             self.d_forward_backward(images)
             self.d_optimizer_step()
         return loss
 
-    def capture(self, images, eps, warmup=2):
-        super().capture(images, eps, warmup=warmup)
+    def capture(self, images, eps, warmup=2, perc_indices=None):
+        super().capture(images, eps, warmup=warmup, perc_indices=perc_indices)
         if self.adversarial:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
@@ -538,8 +593,8 @@ class AEGANTrainer(AETrainer):
                     self.d_optimizer_step()
             self._pinned.append((self.d_arena, dict(ops._ws_cache)))
 
-    def step_graph(self, images=None, eps=None):
-        loss = super().step_graph(images, eps)
+    def step_graph(self, images=None, eps=None, perc_indices=None):
+        loss = super().step_graph(images, eps, perc_indices=perc_indices)
         if self._g_d is not None:
             self._g_d.replay()
             if self.world > 1:

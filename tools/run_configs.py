@@ -1,5 +1,9 @@
 """Run the other BASELINE.json configs through the fused HIP trainer and report ms/step (sanity + scale check).
-usage: python tools/run_configs.py c2|c3a|c3a_gan|c3b|c3b_ldm|c5|c5_ckpt [steps]
+usage: python tools/run_configs.py c2|c3a|c3a_gan|c3a_perc|c3a_perc_extra|c3a_gan_perc|c3b|c3b_ldm|c5|c5_ckpt [steps]
+  c3a_perc: the C3a generator step with the perceptual term (T-AE:416, LPIPS-VGG fake 3-D, ratio 0.2, perc_weight 0.125; random weights)
+           native (AETrainer(perceptual=...), replayed from a hipGraph with fresh slice indices every step);
+  c3a_perc_extra: the same term as AETrainer(extra_loss=...) running the torch fp32 restatement (tests/perc_ref.py) on the GPU, eager
+           (that path cannot be captured); c3a_gan_perc: c3a_gan plus the native perceptual term
   c3a_gan: the autoencoder step AFTER the warm-up epochs -- generator step with the adversarial term through the planner's PatchDiscriminator
            (64 base channels, 3 layers) + the discriminator step (AEGANTrainer), both networks on the HIP path
   c3b_ldm: the latent-diffusion step as train_ldm.py runs it -- no-grad AutoencoderKL.encode_stage_2_inputs of the 4 x 128^3 images
@@ -21,7 +25,7 @@ which = sys.argv[1]
 steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 
 
-def run_c3a(gan=False):
+def run_c3a(gan=False, perc=None):
     """AutoencoderKL exactly as CFG:821-862 emits it for a 128^3 single-channel dataset (BASELINE configs[2], AE half):
     fused generator step (L1 + kl_weight*KL, clip 1, Adam; T-AE:411-434) replayed from a hipGraph."""
     from medical_image_generation_amd.autoencoderkl import AutoencoderKL
@@ -33,31 +37,44 @@ def run_c3a(gan=False):
     dev = torch.device("cuda")
     torch.manual_seed(0)
     net = AutoencoderKL(**kw).to(dev)
+    pk = {}
+    if perc is not None:  # the planner's 3-D perceptual_params (CFG:961-964), perc_weight 0.125 (T-AE:416)
+        from medical_image_generation_amd.perceptual import PerceptualLoss
+        pl = PerceptualLoss(spatial_dims=3, network_type="vgg", is_fake_3d=True, fake_3d_ratio=0.2, pretrained=False).to(dev)
+        if perc == "native":
+            pk = dict(perceptual=pl, perc_weight=0.125)
+        else:
+            from tests import perc_ref
+            pk = dict(extra_loss=lambda rec, img: 0.125 * perc_ref.perceptual(pl, rec, img, pl.draw_indices(tuple(img.shape))))
     if gan:
         from medical_image_generation_amd.discriminator import PatchDiscriminator
         disc = PatchDiscriminator(spatial_dims=3, in_channels=1, out_channels=1, num_channels=64, num_layers_d=3).to(dev)  # CFG:966-967
-        tr = AEGANTrainer(net, disc, adv_weight=0.01, lr=5e-5, d_lr=5e-5, kl_weight=1e-7)
+        tr = AEGANTrainer(net, disc, adv_weight=0.01, lr=5e-5, d_lr=5e-5, kl_weight=1e-7, **pk)
     else:
-        tr = AETrainer(net, lr=5e-5, kl_weight=1e-7)
+        tr = AETrainer(net, lr=5e-5, kl_weight=1e-7, **pk)
     x = torch.rand((2, 1, 128, 128, 128), device=dev)
     eps = torch.randn((2, 8, 32, 32, 32), device=dev)
-    tr.capture(x, eps)
+    graph = perc != "extra"  # (the extra_loss hook runs torch autograd: eager steps only)
+    if graph:
+        tr.capture(x, eps)
+    run = (lambda: tr.step_graph()) if graph else (lambda: tr.step(x, eps))
     for _ in range(2):
-        tr.step_graph()
+        run()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = tr.step_graph()
+        loss = run()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     assert math.isfinite(float(loss)), "non-finite loss: not a measurement"
-    print(json.dumps({"config": "c3a_gan" if gan else "c3a", "ms_per_step": dt * 1e3, "voxels_per_s": 2 * 128 ** 3 / dt, "loss": float(loss),
+    name = ("c3a_gan" if gan else "c3a") + {None: "", "native": "_perc", "extra": "_perc_extra"}[perc]
+    print(json.dumps({"config": name, "graph": graph, "ms_per_step": dt * 1e3, "voxels_per_s": 2 * 128 ** 3 / dt, "loss": float(loss),
                       "params": sum(p.numel() for p in net.parameters()), "model_flops_per_step_survey": 1.497e13,
                       "mfma_frac": 1.497e13 / dt / 2.5e15, "peak_mem_GB": torch.cuda.max_memory_allocated() / 1e9}), flush=True)
 
 
-if which in ("c3a", "c3a_gan"):
-    run_c3a(gan=which == "c3a_gan")
+if which in ("c3a", "c3a_gan", "c3a_perc", "c3a_perc_extra", "c3a_gan_perc"):
+    run_c3a(gan=which.startswith("c3a_gan"), perc={"c3a_perc": "native", "c3a_gan_perc": "native", "c3a_perc_extra": "extra"}.get(which))
     sys.exit(0)
 iso = lambda n: [[1] * 3] + [[2] * 3] * (n - 1)
 if which == "c2":   # 3D DDPM 96^3, batch 2 (BASELINE configs[1])
