@@ -326,7 +326,12 @@ int mi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
                  float* step_counter, hipStream_t stream);
 /* grad_scale: `grad` holds grad_scale^-1 x the gradient -- after a SUM all-reduce over `world` data-parallel ranks pass 1/world and
  * the mean is never materialised (clip_grad_norm_ sees grad_scale * sqrt(grad_sumsq)); 1.0 for a single process.
- * y += alpha * x over fp32 buffers: gradient accumulation over micro-batches (grad_accumulate_step, train_ldm.py:173-180) */
+ * mi_adam_step_dev: mi_adam_step with the hyperparameters in a device block hparams[6] = {lr, beta1, beta2, eps, weight_decay,
+ * max_norm} (fp32) read at run time, so a captured graph follows an lr schedule / a loaded checkpoint; bit-identical results for the
+ * same fp32 values.  grad_sumsq NULL: no clipping (max_norm unused). */
+int mi_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hparams,
+                     int decoupled_weight_decay, const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t stream);
+/* y += alpha * x over fp32 buffers: gradient accumulation over micro-batches (grad_accumulate_step, train_ldm.py:173-180) */
 int mi_axpy_f32(float* y, const float* x, float alpha, int64_t n, hipStream_t stream);
 /* x *= alpha: `latents * inferer.scale_factor` of the latent-diffusion step (train_ldm.py:157) */
 int mi_scale_f32(float* x, float alpha, int64_t n, hipStream_t stream);

@@ -58,6 +58,48 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a) {
   }
 }
 
+// k_adam with the hyperparameters read from a device block {lr, beta1, beta2, eps, weight_decay, max_norm} (uniform scalar loads,
+// once per thread), so a captured graph follows a learning-rate schedule or a loaded checkpoint.  The loop body is k_adam's statement
+// for statement: the compiler then forms the same fused multiply-adds and the results are bit-identical for the same fp32 values
+// (an f32x4 restatement contracted differently and was not).
+struct AdamDevArgs {
+  float* p;
+  const float* g;
+  float* m;
+  float* v;
+  int64_t n;
+  const float* hp;
+  float grad_scale;
+  int decoupled;
+  const float* sumsq;
+  const float* step;
+};
+
+__global__ void __launch_bounds__(256) k_adam_dev(AdamDevArgs a) {
+  const float lr = a.hp[0], beta1 = a.hp[1], beta2 = a.hp[2], eps = a.hp[3], weight_decay = a.hp[4];
+  const float t = *a.step;
+  const float bc1 = 1.f - powf(beta1, t), bc2 = 1.f - powf(beta2, t);
+  const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2);
+  float clip = a.grad_scale;
+  if (a.sumsq) {
+    float c = a.hp[5] / (a.grad_scale * sqrtf(*a.sumsq) + 1e-6f);
+    clip = (c < 1.f ? c : 1.f) * a.grad_scale;
+  }
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
+    float p = a.p[i], g = a.g[i] * clip, m = a.m[i], v = a.v[i];
+    if (a.decoupled)
+      p *= 1.f - lr * weight_decay;
+    else
+      g += weight_decay * p;
+    m = beta1 * m + (1.f - beta1) * g;
+    v = beta2 * v + (1.f - beta2) * g * g;
+    p -= step_size * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
+    a.p[i] = p;
+    a.m[i] = m;
+    a.v[i] = v;
+  }
+}
+
 __global__ void k_step_inc(float* step) { *step += 1.f; }
 __global__ void __launch_bounds__(256) k_scale(float* __restrict__ x, float alpha, int64_t n) {
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] *= alpha;
@@ -106,6 +148,18 @@ int mi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
   int grid = (int)((n + 255) / 256);
   grid = grid > 4096 ? 4096 : grid;
   hipLaunchKernelGGL(k_adam, dim3(grid), dim3(256), 0, st, a);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+
+int mi_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hparams, int decoupled_weight_decay,
+                     const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t st) {
+  if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !hparams || !step_counter || !(grad_scale > 0.f)) return MI_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, st, step_counter);
+  AdamDevArgs a{param, grad, exp_avg, exp_avg_sq, n, hparams, grad_scale, decoupled_weight_decay, grad_sumsq, step_counter};
+  int grid = (int)((n + 255) / 256);
+  grid = grid > 4096 ? 4096 : grid;
+  hipLaunchKernelGGL(k_adam_dev, dim3(grid), dim3(256), 0, st, a);
   MI_CHECK_LAUNCH();
   return 0;
 }

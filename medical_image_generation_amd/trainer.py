@@ -25,6 +25,7 @@ from . import ddp
 from . import engine as E
 from . import hipops as ops
 from ._lib import call, ptr
+from .optim import FusedAdam
 
 F32 = torch.float32
 
@@ -67,12 +68,10 @@ class _ArenaTrainer:
                  grad_accumulate_step=1, overlap=None):
         self.model = model
         self.device = torch.device(device or "cuda")
-        self.lr, self.betas, self.eps = lr, betas, eps
         self.decoupled = optimizer == "AdamW"
         if optimizer not in ("AdamW", "Adam"):
             raise ValueError("optimizer must be 'Adam' or 'AdamW'")
-        self.weight_decay = (0.01 if self.decoupled else 0.0) if weight_decay is None else weight_decay  # torch defaults
-        self.max_grad_norm = max_grad_norm
+        weight_decay = (0.01 if self.decoupled else 0.0) if weight_decay is None else weight_decay  # torch defaults
         self.pg = process_group
         self.world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
         self.bucket_elems = bucket_mb * (1 << 20) // 4
@@ -86,7 +85,11 @@ class _ArenaTrainer:
         self.exp_avg = torch.zeros(n, dtype=F32, device=self.device)
         self.exp_avg_sq = torch.zeros(n, dtype=F32, device=self.device)
         self.step_count = torch.zeros(1, dtype=F32, device=self.device)
-        self.sumsq = torch.zeros(1, dtype=F32, device=self.device)
+        # the torch.optim face of the fused optimizer: torch LR schedulers bind to it (train_ldm.py:124-130); lr / betas / eps /
+        # weight_decay / max_grad_norm below are views of its parameter group
+        self.optimizer = FusedAdam(model, self.arena, self.exp_avg, self.exp_avg_sq, self.step_count, lr, betas, eps, weight_decay,
+                                   self.decoupled, max_grad_norm, 1.0 / self.world)
+        self.sumsq = self.optimizer.sumsq
         self.loss = torch.zeros(1, dtype=F32, device=self.device)
         self._accum = None       # fp32 [n_trainable]: sum of the gradients of the pending micro-steps (grad_accumulate_step > 1)
         self._micro = 0          # micro-steps since the last optimizer step
@@ -95,6 +98,20 @@ class _ArenaTrainer:
         self._force_split = False  # tests: capture the two-graph form with world 1
         self._force_exchange = False  # tests: issue the (one-rank) collectives although world == 1
         self.overlap = (os.environ.get("MI_DDP_OVERLAP", "1") != "0") if overlap is None else bool(overlap)
+
+    # ------------------------------------------------------------------ hyperparameters (self.optimizer's group)
+    lr = property(lambda self: self.optimizer.lr, lambda self, v: setattr(self.optimizer, "lr", v))
+    betas = property(lambda self: self.optimizer.betas, lambda self, v: setattr(self.optimizer, "betas", v))
+    eps = property(lambda self: self.optimizer.eps, lambda self, v: setattr(self.optimizer, "eps", v))
+    weight_decay = property(lambda self: self.optimizer.weight_decay, lambda self, v: setattr(self.optimizer, "weight_decay", v))
+
+    @property
+    def max_grad_norm(self):
+        return self.optimizer.max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):
+        self.optimizer.max_grad_norm = v
 
     # ------------------------------------------------------------------ pieces
     def _forward(self, *inputs):
@@ -145,14 +162,14 @@ class _ArenaTrainer:
             self._exchange().finish()
 
     def optimizer_step(self):
-        a = self.arena
-        n = a.n_trainable
-        clip = self.max_grad_norm is not None and self.max_grad_norm > 0
-        if clip:
-            call("mi_sumsq_f32", ptr(a.grad), n, ptr(self.sumsq), 0)
-        call("mi_adam_step", ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n, self.lr, self.betas[0], self.betas[1],
-             self.eps, self.weight_decay, int(self.decoupled), ptr(self.sumsq) if clip else None, float(self.max_grad_norm or 0.0),
-             1.0 / self.world, ptr(self.step_count))
+        """clip_grad_norm_ + Adam[W] over the arena (self.optimizer.step(): pushes changed hyperparameters, then launches)."""
+        self.optimizer.step()
+
+    @staticmethod
+    def _check_clip(opt, captured):
+        if opt.clip != captured:
+            raise RuntimeError("max_grad_norm was switched on or off after capture(): the captured graph "
+                               f"{'computes' if captured else 'has no'} gradient norm; capture again")
 
     # ------------------------------------------------------------------ gradient accumulation (T-LDM:173-180, T-AE:389-397)
     def _fold_micro_step(self, boundary):
@@ -216,9 +233,11 @@ class _ArenaTrainer:
             with torch.cuda.graph(self._g_fb2, pool=self._g_fb.pool(), capture_error_mode="thread_local"):
                 self._fb_finish(state)
             del state
+        self.optimizer.push()  # the graph reads the hyperparameters from the device block; step_graph() keeps it current
+        self._clip_captured = self.optimizer.clip
         self._g_opt = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g_opt, capture_error_mode="thread_local"):
-            self.optimizer_step()
+            self.optimizer.launch()
         self._graph = True
         # The graphs hold raw device pointers of objects Python owns: the PackBatch (group tables), every conv plan (packed weights,
         # split slabs), the GroupNorm workspace and the arena.  Pin them for as long as the graphs exist -- a forward at another
@@ -247,7 +266,8 @@ class _ArenaTrainer:
             self._g_fb2.replay()   # ... and its all-reduce runs over xGMI while the rest of the backward computes
         if ex is not None:
             ex.finish()
-        self._g_opt.replay()
+        self._check_clip(self.optimizer, self._clip_captured)
+        self.optimizer.step(replay=self._g_opt)  # block refreshed first: a scheduler / load_model between replays takes effect
         return self.loss
 
 
@@ -515,17 +535,32 @@ class AEGANTrainer(AETrainer):
         self.d_arena = discriminator.arena(self.device)
         if self.world > 1:
             ddp.broadcast_parameters(self.d_arena.data, 0, self.pg)
-        self.adv, self.adv_weight, self.d_lr = PatchAdversarialLoss("least_squares"), float(adv_weight), float(d_lr)
+        self.adv, self.adv_weight = PatchAdversarialLoss("least_squares"), float(adv_weight)
         self.adversarial = bool(adversarial)
         n = self.d_arena.n_trainable
         self.d_exp_avg = torch.zeros(n, dtype=F32, device=self.device)
         self.d_exp_avg_sq = torch.zeros(n, dtype=F32, device=self.device)
         self.d_step_count = torch.zeros(1, dtype=F32, device=self.device)
-        self.d_sumsq = torch.zeros(1, dtype=F32, device=self.device)
+        # torch.optim.Adam(discriminator.parameters(), lr=d_lr) (T-AE:471): the generator's betas / eps / clip norm, no weight decay
+        self.d_optimizer = FusedAdam(discriminator, self.d_arena, self.d_exp_avg, self.d_exp_avg_sq, self.d_step_count, d_lr, self.betas,
+                                     self.eps, 0.0, False, self.max_grad_norm, 1.0 / self.world)
+        self.d_sumsq = self.d_optimizer.sumsq
         self.gen_loss = torch.zeros(1, dtype=F32, device=self.device)   # adv_weight * LS(D(recon), real) of the last generator step
         self.disc_loss = torch.zeros(1, dtype=F32, device=self.device)  # adv_weight * 0.5 (fake + real) of the last discriminator step
         self.recon_cl = None
         self._g_d = None
+
+    d_lr = property(lambda self: self.d_optimizer.lr, lambda self, v: setattr(self.d_optimizer, "lr", v))
+
+    @property
+    def max_grad_norm(self):
+        return self.optimizer.max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, v):  # one clip norm for both networks (T-AE:393, 431)
+        self.optimizer.max_grad_norm = v
+        if hasattr(self, "d_optimizer"):
+            self.d_optimizer.max_grad_norm = v
 
     def _models(self):
         return [self.model]
@@ -559,16 +594,14 @@ class AEGANTrainer(AETrainer):
             c.tape.backward(logits, dl)
             c.tape.grads.clear(), c.tape.keep.clear()
 
-    def d_optimizer_step(self):
-        a = self.d_arena
-        n = a.n_trainable
+    def _d_exchange(self):
         if self.world > 1:
-            ddp.GradientExchange(a.grad, 0, n, self.pg, self.bucket_elems).finish()
-        clip = self.max_grad_norm is not None and self.max_grad_norm > 0
-        if clip:
-            call("mi_sumsq_f32", ptr(a.grad), n, ptr(self.d_sumsq), 0)
-        call("mi_adam_step", ptr(a.data), ptr(a.grad), ptr(self.d_exp_avg), ptr(self.d_exp_avg_sq), n, self.d_lr, self.betas[0], self.betas[1],
-             self.eps, 0.0, 0, ptr(self.d_sumsq) if clip else None, float(self.max_grad_norm or 0.0), 1.0 / self.world, ptr(self.d_step_count))
+            a = self.d_arena
+            ddp.GradientExchange(a.grad, 0, a.n_trainable, self.pg, self.bucket_elems).finish()
+
+    def d_optimizer_step(self):
+        self._d_exchange()
+        self.d_optimizer.step()
 
     def step(self, images, eps, last_in_epoch=False, perc_indices=None):
         loss = super().step(images, eps, perc_indices=perc_indices)
@@ -578,6 +611,17 @@ class AEGANTrainer(AETrainer):
         return loss
 
     def capture(self, images, eps, warmup=2, perc_indices=None):
+        """The warm-up passes run the discriminator in training mode on whatever the graph pool holds; its BatchNorm running buffers
+        are restored afterwards, so capture() leaves them (and checkpoints of them) exactly as they were."""
+        bn = [b.clone() for b in self.D.buffers()]
+        try:
+            self._capture(images, eps, warmup, perc_indices)
+        finally:
+            torch.cuda.synchronize()
+            for b, s in zip(self.D.buffers(), bn):
+                b.copy_(s)
+
+    def _capture(self, images, eps, warmup, perc_indices):
         super().capture(images, eps, warmup=warmup, perc_indices=perc_indices)
         if self.adversarial:
             s = torch.cuda.Stream()
@@ -586,17 +630,22 @@ class AEGANTrainer(AETrainer):
                 self.d_forward_backward(self._static[0])
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
+            self.d_optimizer.push()
+            self._d_clip_captured = self.d_optimizer.clip
             self._g_d = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self._g_d, pool=self._g_fb.pool(), capture_error_mode="thread_local"):
                 self.d_forward_backward(self._static[0])
                 if self.world <= 1:
-                    self.d_optimizer_step()
+                    self.d_optimizer.launch()
             self._pinned.append((self.d_arena, dict(ops._ws_cache)))
 
     def step_graph(self, images=None, eps=None, perc_indices=None):
         loss = super().step_graph(images, eps, perc_indices=perc_indices)
         if self._g_d is not None:
-            self._g_d.replay()
+            self._check_clip(self.d_optimizer, self._d_clip_captured)
             if self.world > 1:
+                self._g_d.replay()
                 self.d_optimizer_step()
+            else:
+                self.d_optimizer.step(replay=self._g_d)  # discriminator forward / backward + its optimizer, block refreshed first
         return loss
