@@ -144,6 +144,9 @@ class HipModule(nn.Module):
 
     def arena(self, device) -> E.ParamArena:
         """(Re)bind every nn.Parameter to a view of one flat device buffer; idempotent while nothing moved."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:  # "cuda" and "cuda:<current>" are one device: same arena
+            device = torch.device("cuda", torch.cuda.current_device())
         params = dict(self.named_parameters())
         a = self._arena
         first = self._entries[0][0]
