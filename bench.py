@@ -2,7 +2,11 @@
 
 One JSON line on rank 0 (contract in the task statement).  A "step" = noise -> q-sample -> UNet forward -> MSE ->
 backward -> (gradient all-reduce) -> clip_grad_norm_ -> AdamW on one synthetic batch already resident in HBM.
-  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full [--no-cpu-baseline]]
+A plain run sets up, warms up, times the K steps and prints the line: the headline figure, the run's configuration and the loss.
+--full adds what takes runs of its own after the timed steps: the step's model flops and MFMA fraction, the two dominant conv kernels
+timed alone against the MFMA peak (roofline, roofline_fwd), a per-entry-point breakdown of one eager step and, unless
+--no-cpu-baseline, the CPU oracle timed on the same workload (about a minute).
 --dump-outputs DIR writes what the last timed step computed (dump_outputs) as DIR/<name>.npy; the inputs (weights, volume, noise and
 timestep draws) are seeded, so two builds run with the same arguments can be compared output for output.
 N > 1: one rank per GPU over RCCL -- either started by `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...`
@@ -168,6 +172,29 @@ def dump_outputs(out_dir, net, tr, loss):
         np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
+def full_figures(args, net, tr, x0, noise, t, dt, world):
+    """What --full adds to the line, each from runs of its own after the timed steps: the step's algorithmic flops and MFMA fraction,
+    the two dominant conv kernels timed alone, one eager step by C-ABI entry point and the CPU baseline (single-GPU runs only)."""
+    from medical_image_generation_amd import engine as E
+    # algorithmic flops of one step of this model (engine counters: 2*MACs, bwd = dgrad + wgrad)
+    c = E.Ctx(tr.arena, net._plans, grad_enabled=True)
+    net._run(c, torch.zeros((args.batch, args.size, args.size, args.size, 1), dtype=torch.bfloat16, device=x0.device), t, need_dx=False)
+    c.tape.fns.clear()
+    step_flops = c.flops_fwd + c.flops_bwd
+    del c
+    out = {
+        "model_flops_per_step": step_flops,
+        "step_mfma_frac": step_flops / (dt / args.steps) / MFMA_PEAK_BF16,
+        "roofline": kernel_roofline("wgrad", args.size),      # largest kernel of the step by total time
+        "roofline_fwd": kernel_roofline("fwd", args.size),    # second largest (forward and dgrad share it)
+    }
+    if world == 1:
+        out["step_breakdown_ms"] = step_breakdown(tr, x0, noise, t)
+    if world == 1 and not args.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -176,7 +203,9 @@ def main():
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--batch", type=int, default=1, help="per-GPU batch")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure step flops, the kernel rooflines, an eager step breakdown and "
+                                                          "the CPU baseline (runs of their own after the timed steps)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--roofline-only", action="store_true", help="only time the dominant kernels (for rocprofv3 cross-checks)")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss, parameters and gradients (sampled) to DIR")
     args = ap.parse_args()
@@ -271,18 +300,9 @@ def main():
         raise RuntimeError(f"bench: non-finite loss / parameters after the timed steps (loss = {float(loss)}): refusing to report a number")
 
     if rank == 0 and args.dump_outputs:
-        dump_outputs(args.dump_outputs, net, tr, loss)  # before step_breakdown below, which runs one more (eager) step
+        dump_outputs(args.dump_outputs, net, tr, loss)  # before --full's figures, whose step breakdown runs one more (eager) step
 
     if rank == 0:
-        # algorithmic flops of one step of this model (engine counters: 2*MACs, bwd = dgrad + wgrad)
-        from medical_image_generation_amd import engine as E
-        c = E.Ctx(tr.arena, net._plans, grad_enabled=True)
-        net._run(c, torch.zeros((args.batch, args.size, args.size, args.size, 1), dtype=torch.bfloat16, device=dev), t, need_dx=False)
-        c.tape.fns.clear()
-        step_flops = c.flops_fwd + c.flops_bwd
-        del c
-        roof = kernel_roofline("wgrad", args.size)       # largest kernel of the step by total time
-        roof_fwd = kernel_roofline("fwd", args.size)     # second largest (forward and dgrad share it)
         out = {
             "metric": "3D DDPM U-Net train-step voxels/sec at 128^3 bf16", "value": voxels / dt, "unit": "voxels/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3,
@@ -290,19 +310,13 @@ def main():
             "config": {"workload": f"C4: DiffusionModelUNet num_channels=(32,64,128,256), attention at 16^3 (heads of 64), "
                                    f"{args.size}^3 x batch {args.batch}/GPU, eps-prediction, AdamW, clip 1.0",
                        "global_batch": world * args.batch, "parallelism": f"dp{world}", "hipgraph": use_graph},
-            "model_flops_per_step": step_flops,
-            "step_mfma_frac": step_flops / (dt / args.steps) / MFMA_PEAK_BF16,
             "loss": float(loss),
-            "roofline": roof,
-            "roofline_fwd": roof_fwd,
         }
-        if world == 1:
-            out["step_breakdown_ms"] = step_breakdown(tr, x0, noise, t)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline()
+        if args.full:
+            out.update(full_figures(args, net, tr, x0, noise, t, dt, world))
         print(json.dumps(out), flush=True)
     if world > 1:
-        dist.barrier()  # rank 0 is still timing the roofline kernels when the others get here: tear the group down together
+        dist.barrier()  # with --full, rank 0 is still timing the roofline kernels when the others get here: leave together
         dist.destroy_process_group()
 
 

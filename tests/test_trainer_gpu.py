@@ -536,6 +536,41 @@ def test_bench_two_ranks_child_process():
     assert rec["config"]["hipgraph"] is True
 
 
+def test_bench_plain_line_and_full_figures():
+    """A plain `python bench.py` prints the headline line and nothing that takes runs of its own; `--full` adds the step's flops and
+    MFMA fraction, the two kernel rooflines and the eager step breakdown (the CPU baseline left out here: it takes a minute), over the
+    same timed steps."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    recs = []
+    for extra in ([], ["--full", "--no-cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--size", "32", "--steps", "2", "--warmup", "1"] + extra,
+                           cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs.append(json.loads(lines[0]))
+    plain, full = recs
+    extras = ("model_flops_per_step", "step_mfma_frac", "roofline", "roofline_fwd", "step_breakdown_ms")
+    for rec in recs:
+        assert rec["metric"] == "3D DDPM U-Net train-step voxels/sec at 128^3 bf16" and rec["unit"] == "voxels/s"
+        assert rec["higher_is_better"] is True and rec["dtype"] == "bf16" and rec["steps"] == 2 and rec["warmup"] == 1
+        assert rec["ms_per_step"] > 0 and abs(rec["value"] - 32 ** 3 * 1e3 / rec["ms_per_step"]) <= 1e-6 * rec["value"]
+        assert rec["config"]["hipgraph"] is True and rec["loss"] == rec["loss"] and "cpu_baseline" not in rec
+    assert not any(k in plain for k in extras)
+    assert all(k in full for k in extras)
+    assert full["model_flops_per_step"] > 0 and 0 < full["step_mfma_frac"] < 1
+    assert full["roofline"]["avg_launch_us"] > 0 and full["roofline_fwd"]["avg_launch_us"] > 0 and full["step_breakdown_ms"]["sum"] > 0
+    # seeded inputs and weights: the two runs time the same steps (fp32-atomic summation order aside)
+    assert abs(plain["loss"] - full["loss"]) <= 1e-3 * abs(plain["loss"])
+
+
 def test_graph_survives_other_shape_forward():
     """a captured train step holds raw pointers into the PackBatch / conv plans / GroupNorm workspace; a forward at
     another shape between train steps (validation, sampling) used to replace and free them.  capture -> sample at another batch
