@@ -283,6 +283,24 @@ int mi_relu_maxpool2_bwd(const void* a, const void* dpooled, const void* dadd, v
 int mi_lpips_head(const void* f0, const void* f1, const float* w, int S, int64_t P, int C, float weight, float eps, float* loss, void* df0,
                   hipStream_t stream);
 
+/* ---- SSIM / MS-SSIM of the sample-diversity scores (train_ldm.py:276-277 `MultiScaleSSIMMetric(...)` / `SSIMMetric(...)`, :315-321
+ * every unordered pair of the sampled images; third-party `generative.metrics` classes: PARITY UNPINNED).  Images are fp32
+ * [N][C][D][H][W] (2-D: D = 1); a pair (a, b) scores image a of the x base against image b of the y base.  Separable VALID filter of at
+ * most 11 taps per axis; taps: fp32 [kD + kH + kW] (axis D first; 2-D: kD = 1, tap 1). */
+/* output tiles per channel of one scale (0: a kernel larger than the extent or than 11 taps); the partial rows are sized from it */
+int mi_ssim_tiles(int D, int H, int W, int kD, int kH, int kW);
+/* partials[pair][part_off + tile] = {sum ssim, sum cs} (fp64) over the tile's valid voxels, tile < C * mi_ssim_tiles(...);
+ * pairs: int32 [P][2]; rows of part_stride tiles (the scales of one pass side by side); MI_ERR_UNSUPPORTED above 11 taps */
+int mi_ssim_pairs(const float* x_base, const float* y_base, const int* pairs, int P, int C, int D, int H, int W, const float* taps, int kD,
+                  int kH, int kW, float c1, float c2, double* partials, int part_stride, int part_off, hipStream_t stream);
+/* y = floor 2x average pool (kernel 2, stride 2) of x over H, W and, when pool_d, D; x [NC][D][H][W] fp32 (F.avg_pool2d / 3d) */
+int mi_ssim_pool2(const float* x, float* y, int64_t NC, int D, int H, int W, int pool_d, hipStream_t stream);
+/* per pair, scales 0 .. S-1 in order (host_tiles[s] partial tiles each, host_counts[s] = C * valid voxels): mean ssim / cs in fp64;
+ * ssim_out[pair] (may be NULL) = mean ssim of scale 0; ms_out[pair] (may be NULL) = prod_s relu(m_s) ^ host_weights[s] with m_s the
+ * mean cs, the mean ssim at s = S-1.  S <= 8 */
+int mi_ssim_finalize(const double* partials, int P, int part_stride, int S, const int* host_tiles, const double* host_counts,
+                     const double* host_weights, float* ms_out, float* ssim_out, hipStream_t stream);
+
 /* ---- train-step glue: scheduler.add_noise (T-LDM:160), F.mse_loss (+backward) (T-LDM:169, T-DDPM:192) ------------------- */
 int mi_qsample(const float* x0, const float* noise, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod,
                const int64_t* timesteps, const float* cond, int cond_channels, void* out, float* velocity, int N, int C, int64_t V,

@@ -92,6 +92,10 @@ _SIGS = {
     "mi_relu_maxpool2_fwd": [_p, _p, _i, _i, _i, _i, _p],
     "mi_relu_maxpool2_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
     "mi_lpips_head": [_p, _p, _p, _i, _l, _i, _f, _f, _p, _p, _p],
+    "mi_ssim_tiles": [_i, _i, _i, _i, _i, _i],
+    "mi_ssim_pairs": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _f, _f, _p, _i, _i, _p],
+    "mi_ssim_pool2": [_p, _p, _l, _i, _i, _i, _i, _p],
+    "mi_ssim_finalize": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
     "mi_leaky_relu_fwd": [_p, _p, _l, _f, _p],
     "mi_leaky_relu_bwd": [_p, _p, _p, _l, _f, _p],
     "mi_ls_gan_loss": [_p, _i, _l, _f, _f, _p, _p, _f, _p],
@@ -110,13 +114,13 @@ _SIGS = {
     "mi_scale_f32": [_p, _f, _l, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l}
-_NOCHECK = {"mi_abi_version", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks"}
+_NOCHECK = {"mi_abi_version", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks"}
 
 _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 def exported_symbols() -> list[str]:
