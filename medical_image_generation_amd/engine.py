@@ -1,9 +1,9 @@
 """Tape engine: forward ops on channels-last bf16 activations that record their own HIP backward.
 
 Why not one torch.autograd.Function per kernel: the fused kernels need to know about each other
-(GroupNorm statistics feed the NEXT conv's prologue; the conv's data gradient feeds the GroupNorm/SiLU
-backward which also folds in the other gradient branches of the same tensor), and gradient accumulation
-must run through our kernels, not aten::add.  The tape gives that control; `functional.py` wraps whole
+(a conv's epilogue emits the channel sums the NEXT GroupNorm's statistics come from; the conv's data gradient
+feeds the GroupNorm/SiLU backward which also folds in the other gradient branches of the same tensor), and
+gradient accumulation must run through our kernels, not aten::add.  The tape gives that control; `functional.py` wraps whole
 blocks / networks of it as torch.autograd.Function for callers that want autograd.
 
 Everything here launches HIP kernels through hipops; torch only allocates (torch.empty / views).
@@ -21,102 +21,13 @@ from ._lib import call, ptr
 
 BF16, F32 = torch.bfloat16, torch.float32
 
-# GroupNorm(+SiLU) in front of a conv: either fused into the conv's staging (no activated tensor in HBM, but the
-# transcendental is evaluated on 2.3x halo-inflated data in forward AND in wgrad) or one standalone apply pass whose bf16
-# output both kernels read.  Measured on MI355X (tools/bench_conv.py): fused costs +85 us per 32-channel 128^3 conv per
-# use, the standalone pass 54 us once -> standalone is the default; MI_FUSE_PROLOGUE=1 selects the fused path.
 import os as _os
-FUSE_PROLOGUE = _os.environ.get("MI_FUSE_PROLOGUE", "0") == "1"
+# Backward schedules that were measured and not kept (second-stream or deferred weight gradients, data gradient first, the two-launch
+# GroupNorm backward, GroupNorm+SiLU inside the conv's staging) are recorded in EXPERIMENTS.md.
 # Fused (flash-style) attention for head dims 32 / 64; MI_FLASH_ATTENTION=0 forces the materialised GEMM + softmax path.
 FLASH_ATTENTION = _os.environ.get("MI_FLASH_ATTENTION", "1") == "1"
 # GroupNorm statistics from the per-channel sums the producing conv's epilogue emits (no statistics pass over the tensor)
 FUSE_GN_STATS = ops.FUSE_GN_STATS
-# A/B knob, default OFF: GroupNorm backward in two launches (partial sums by fp64 atomics into a per-pass zeroed buffer, coefficients
-# derived inside the apply pass: mi_gn_bwd_fused) instead of three.  It removes the 51 finalize launches of a C4 step (~9 us each) and
-# is SLOWER: 22.46 -> 23.47 ms/step (round 3, profiles/r03k_ab_gn_fused.log, same box, interleaved) -- 1024 blocks adding to the same
-# 64 addresses serialise at the memory side for about as long as the finalize launch took, and every apply thread now starts with a
-# dependent L2 round trip for its coefficients.
-GN_BWD_FUSED = _os.environ.get("MI_GN_BWD_FUSED", "0") == "1"
-# ... or only for tensors of at most this many voxels per image (the coarse levels: few blocks, so few atomics per address; there the
-# finish launch it saves is a large part of the three-launch backward).  0 = off.
-GN_BWD_FUSED_MAXV = int(_os.environ.get("MI_GN_BWD_FUSED_MAXV", "0"))
-
-
-# A/B knob, default OFF: weight gradients of the layers whose kernels cannot fill the chip on a second stream.  A conv's data gradient
-# and weight gradient only share their inputs; at the coarsest level of a batch-1 step (16^3 voxels x 256 channels: 16 tiles x 8
-# channel blocks) each is a launch of 128 single-tile workgroups on 256 CUs, so the two could run side by side (captured into the
-# hipGraph as two branches).  Measured (round 3, profiles/r03f_ab_side.log, same box, interleaved): 22.70 / 22.80 ms/step on one stream,
-# 23.35 / 23.36 with the fork for plans of <= 160 workgroups, 23.35 / 23.42 for <= 300: the fork / join edges of 14 layers cost more
-# than the overlap returns (round 2 measured the same for a fork of every layer).
-SIDE_WGRAD = _os.environ.get("MI_SIDE_WGRAD", "0") == "1"
-# MI_SIDE_WGRAD=2: the OTHER overlap -- chip-filling layers only.  A conv's weight gradient (MFMA-bound, one persistent workgroup of 168
-# registers x 8 waves per CU: room for other waves beside it) is forked BEHIND its data gradient, so that it runs beside the GroupNorm
-# backward of the conv's input (HBM-bound streaming kernels without LDS) instead of beside the data gradient (which needs the same LDS).
-SIDE_BESIDE_NORM = _os.environ.get("MI_SIDE_WGRAD", "0") == "2"
-SIDE_MIN_WGS = int(_os.environ.get("MI_SIDE_MIN_WGS", "256"))
-DGRAD_FIRST = _os.environ.get("MI_DGRAD_FIRST", "0") == "1"  # data gradient before the weight gradient of a conv (default: after)
-SIDE_MAX_WGS = int(_os.environ.get("MI_SIDE_MAX_WGS", "160"))
-# A/B knob: the same weight gradients DEFERRED instead -- queued while the backward walks the coarse levels, then launched together on
-# the side stream with ONE fork when the first layer with a chip-filling grid comes up (and one join at the cut mark / the end of the
-# backward): the latency-bound launches of the 16^3 level (each ~40 us for ~10 us of work) run beside the finer levels' kernels.
-DEFER_WGRAD = _os.environ.get("MI_DEFER_WGRAD", "0") == "1"
-DEFER_MAX_TILES = int(_os.environ.get("MI_DEFER_MAX_TILES", "64"))  # layers of at most this many 4 x 8 x 8 output tiles are queued
-_side_streams: dict = {}
-_side_pending: set = set()  # devices whose side stream has work the main stream has not waited for
-_deferred: dict = {}        # device index -> [(closure, tensors it reads)] in backward order
-
-
-def _dev_index(device):
-    device = torch.device(device)
-    return torch.cuda.current_device() if device.index is None else device.index
-
-
-def _side_stream(device):
-    i = _dev_index(device)
-    st = _side_streams.get(i)
-    if st is None:
-        st = _side_streams[i] = torch.cuda.Stream(device=i)
-    return st
-
-
-def flush_deferred(device):
-    """Launch the queued weight gradients on the side stream, behind everything the current stream holds so far."""
-    i = _dev_index(device)
-    q = _deferred.get(i)
-    if not q:
-        return
-    side = _side_stream(i)
-    side.wait_stream(torch.cuda.current_stream(i))
-    with torch.cuda.stream(side):
-        for fn, _ in q:
-            fn()
-    for _, tensors in q:
-        for t in tensors:
-            t.record_stream(side)  # (freed blocks must not be handed out again under the side kernels)
-    q.clear()
-    _side_pending.add(i)
-
-
-def join_side(device):
-    """The current stream waits for everything forked onto the side stream (before anything reads a weight / bias gradient)."""
-    i = _dev_index(device)
-    flush_deferred(i)
-    if i in _side_pending:
-        torch.cuda.current_stream(i).wait_stream(_side_stream(i))
-        _side_pending.discard(i)
-
-
-def _tiles(plan):
-    od, oh, ow = plan.out_dims if not isinstance(plan, ops.UpConvPlan) else plan.dims
-    return plan.n * ((od + 3) // 4) * ((oh + 7) // 8) * ((ow + 7) // 8)
-
-
-def _small_grid(plan):
-    return plan.out_dims[0] > 1 and _tiles(plan) * ((max(plan.cin, plan.cout) + 31) // 32) <= SIDE_MAX_WGS
-
-
-def _coarse(plan):
-    return plan.out_dims[0] > 1 and _tiles(plan) <= DEFER_MAX_TILES
 
 
 # --------------------------------------------------------------------------------------------- parameters
@@ -224,7 +135,6 @@ class Tape:
         for fn in reversed(self.fns):
             fn()
         self.fns.clear()
-        join_side(out.device)
 
 
 class Ctx:
@@ -243,21 +153,6 @@ class Ctx:
         # CPython reuses ids), so every lookup checks that the weak reference still IS the tensor asked about.
         self.sums = {}
         self.cat_parts = {}
-        self._z64 = None   # zeroed fp64 scratch of this pass (zeros64): cleared by ONE fill, handed out in slices
-        self._z64_off = 0
-
-    def zeros64(self, numel, device, voxels=None):
-        """A zeroed fp64 slice for a kernel that accumulates with atomics (the fused GroupNorm backward): carved from a buffer that one
-        fill per pass clears, so that no norm needs a zero-fill node of its own.  None when the fused form is off for this size."""
-        if not (GN_BWD_FUSED or (voxels is not None and voxels <= GN_BWD_FUSED_MAXV)):
-            return None
-        numel = (numel * ops.GN_FUSED_REPLICAS + 31) // 32 * 32  # (the kernel spreads its atomics over up to that many records)
-        if self._z64 is None or self._z64_off + numel > self._z64.numel():
-            self._z64 = torch.zeros(max(1 << 20, numel), dtype=torch.float64, device=device)  # 8 MiB: the ~50 norms of a C4 pass take 4
-            self._z64_off = 0
-        out = self._z64[self._z64_off:self._z64_off + numel]
-        self._z64_off += numel
-        return out
 
     def sums_of(self, x):
         ent = self.sums.get(id(x))
@@ -308,7 +203,7 @@ class PackBatch:
 
 # --------------------------------------------------------------------------------------------- ops
 def gn(ctx: Ctx, x, name, groups, eps):
-    """Statistics only; the affine(+SiLU) is applied by the consumer (conv prologue or gn_apply)."""
+    """Statistics only; the affine(+SiLU) is applied by the consumer (conv or gn_act)."""
     gamma, beta = ctx.p(name + ".weight"), ctx.p(name + ".bias")
     st = None
     if FUSE_GN_STATS:
@@ -388,10 +283,10 @@ def conv_transpose(ctx: Ctx, x, name, kernel, stride, padding):
 def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addvec=None, res=None, d_addvec=None,
          need_dx=True, bias_grad_like=None, out=None, upconv=False):
     """y = conv(act(x)) + addvec + res   (weight `name.weight`, bias folded into addvec by the caller or taken from
-    `name.bias` when addvec is None).  norm: GNStats of x for the fused prologue.  d_addvec: fp32 [N, Cout] view that
-    receives the per-sample column sums of dy (time-embedding gradient) in backward.  bias_grad_like: name of a conv whose
-    output gradient is THIS conv's output gradient (a shortcut conv added as `res` of that conv): its bias gradient, already
-    computed when this backward runs, is copied instead of reducing dy a second time."""
+    `name.bias` when addvec is None).  norm: GNStats of x, applied (+ SiLU) by one gn_apply pass in front of the conv.
+    d_addvec: fp32 [N, Cout] view that receives the per-sample column sums of dy (time-embedding gradient) in backward.
+    bias_grad_like: name of a conv whose output gradient is THIS conv's output gradient (a shortcut conv added as `res` of
+    that conv): its bias gradient, already computed when this backward runs, is copied instead of reducing dy a second time."""
     n, d, h, w, cin = x.shape
     wt = ctx.p(name + ".weight")
     cout = wt.shape[0]
@@ -403,11 +298,8 @@ def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addv
         plan.pack(wt)  # [Cout, Cin, (kd,) kh, kw] contiguous: same memory layout for 2-D and 3-D nets
         ctx.packed.add(key)
     av = addvec if addvec is not None else ctx.p(name + ".bias")
-    if norm is not None and not FUSE_PROLOGUE:
-        xin, pn, ps = ops.gn_apply(x, norm, silu), None, False
-    else:
-        xin, pn, ps = x, norm, silu
-    y, sums = plan.fwd(xin, pn, ps, addvec=av, res=res, out=out, want_sums=True)  # out: channel-slice view of the consumer's concat buffer
+    xin = ops.gn_apply(x, norm, silu) if norm is not None else x
+    y, sums = plan.fwd(xin, addvec=av, res=res, out=out, want_sums=True)  # out: channel-slice view of the consumer's concat buffer
     if sums is not None:
         ctx.sums[id(y)] = (sums, weakref.ref(y))
     ctx.count(2 * y.numel() * cin * math.prod(kernel), dgrad=need_dx)
@@ -422,42 +314,19 @@ def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addv
             # column sums of dy come out of the wgrad kernel (one extra MFMA per k-step on the dY fragments it holds anyway):
             # per image into `d_addvec` (time-embedding gradient; the caller folds the rows into the bias gradient), or --
             # row pitch 0 -- summed over the batch straight into the bias gradient
-            def wgrad():
-                if bias_grad_like is not None:
-                    plan.wgrad(xin, dy, gw, pn, ps)
-                    ops.add_f32_(ctx.g(name + ".bias"), ctx.g(bias_grad_like + ".bias"))
-                else:
-                    plan.wgrad(xin, dy, gw, pn, ps, colsum=d_addvec if d_addvec is not None else ctx.g(name + ".bias"))
-
-            beside_norm = (SIDE_BESIDE_NORM and need_dx and norm is not None and plan.out_dims[0] > 1 and
-                           _tiles(plan) * ((max(plan.cin, plan.cout) + 31) // 32) >= SIDE_MIN_WGS)
-            g_early = plan.dgrad(dy) if ((DGRAD_FIRST or beside_norm) and need_dx) else None  # (A/B: which of the two readers of dy runs first)
-            di = _dev_index(dy.device)
-            if SIDE_BESIDE_NORM and not beside_norm and bias_grad_like is not None:
-                join_side(dy.device)  # (the bias gradient this layer copies may still be in flight on the side stream)
-            if DEFER_WGRAD and need_dx and (_coarse(plan) or (bias_grad_like is not None and _deferred.get(di))):
-                # (a shortcut conv copies the bias gradient its block's conv2 produces: it queues up behind a queued conv2)
-                _deferred.setdefault(di, []).append((wgrad, (xin, dy)))
-            elif DEFER_WGRAD and _deferred.get(di):
-                flush_deferred(di)
-                wgrad()
-            elif beside_norm or (SIDE_WGRAD and need_dx and bias_grad_like is None and _small_grid(plan)):
-                dev, side = dy.device, _side_stream(dy.device)
-                side.wait_stream(torch.cuda.current_stream(dev))  # dy (and everything before it) is ready
-                with torch.cuda.stream(side):
-                    wgrad()
-                xin.record_stream(side), dy.record_stream(side)    # (freed blocks must not be handed out again under the side kernel)
-                _side_pending.add(_dev_index(dev))
+            if bias_grad_like is not None:
+                plan.wgrad(xin, dy, gw)
+                ops.add_f32_(ctx.g(name + ".bias"), ctx.g(bias_grad_like + ".bias"))
             else:
-                wgrad()
+                plan.wgrad(xin, dy, gw, colsum=d_addvec if d_addvec is not None else ctx.g(name + ".bias"))
             if res is not None:
                 tape.put(res, dy)
             if need_dx:
-                g = g_early if g_early is not None else plan.dgrad(dy)
+                g = plan.dgrad(dy)
                 if norm is not None:
                     other, other2 = tape.take2(x)
                     dx = ops.gn_bwd(g, x, norm, ctx.p(norm.name + ".weight"), silu, ctx.g(norm.name + ".weight"),
-                                    ctx.g(norm.name + ".bias"), add=other, add2=other2, sums=ctx.zeros64(2 * x.shape[0] * x.shape[-1], x.device, x.shape[1] * x.shape[2] * x.shape[3]))
+                                    ctx.g(norm.name + ".bias"), add=other, add2=other2)
                     tape.grads[id(x)] = dx
                     tape.keep.append(x)
                 else:
@@ -534,8 +403,8 @@ def avg_pool(ctx: Ctx, x, kernel, stride):
 
 
 def gn_act(ctx: Ctx, x, st, silu):
-    """act(GroupNorm(x)) as a tensor of its own (for consumers other than a conv prologue: the resamplers of
-    ResnetBlock(up / down), UNet:679-687).  Backward folds the other gradient branches of x in, like conv's fused path."""
+    """act(GroupNorm(x)) as a tensor of its own (for consumers other than a conv, which applies its own norm: the resamplers of
+    ResnetBlock(up / down), UNet:679-687).  Backward folds the other gradient branches of x in, like conv's backward."""
     y = ops.gn_apply(x, st, silu)
     if ctx.tape is not None:
         tape = ctx.tape
@@ -545,8 +414,8 @@ def gn_act(ctx: Ctx, x, st, silu):
             if g is None:
                 return
             other, other2 = tape.take2(x)
-            dx = ops.gn_bwd(g, x, st, ctx.p(st.name + ".weight"), silu, ctx.g(st.name + ".weight"), ctx.g(st.name + ".bias"), add=other,
-                            add2=other2, sums=ctx.zeros64(2 * x.shape[0] * x.shape[-1], x.device, x.shape[1] * x.shape[2] * x.shape[3]))
+            dx = ops.gn_bwd(g, x, st, ctx.p(st.name + ".weight"), silu, ctx.g(st.name + ".weight"), ctx.g(st.name + ".bias"),
+                            add=other, add2=other2)
             tape.grads[id(x)] = dx
             tape.keep.append(x)
 
@@ -706,8 +575,7 @@ def _attention_param_and_input_grads(ctx, tape, x, name, st, xn, wqkv, dqkv, dy,
     dxn = torch.empty(x.shape, dtype=BF16, device=dev)
     _gemm(dqkv, 3 * c, 0, 0, wqkv_t, 3 * c, 0, 0, dxn, c, 0, 0, b * s, c, 3 * c, 1, 1)
     other = tape.take(x)
-    dx = ops.gn_bwd(dxn, x, st, ctx.p(pre + "norm.weight"), False, ctx.g(pre + "norm.weight"), ctx.g(pre + "norm.bias"), add=dy, add2=other,
-                    sums=ctx.zeros64(2 * x.shape[0] * x.shape[-1], x.device, x.shape[1] * x.shape[2] * x.shape[3]))
+    dx = ops.gn_bwd(dxn, x, st, ctx.p(pre + "norm.weight"), False, ctx.g(pre + "norm.weight"), ctx.g(pre + "norm.bias"), add=dy, add2=other)
     tape.grads[id(x)] = dx
     tape.keep.append(x)
 

@@ -224,7 +224,7 @@ GN_FUSED_REPLICAS = 16  # MI_GN_FUSED_REPLICAS of include/medimgen_hip.h
 
 def gn_bwd(g, x, st: GNStats, gamma, silu: bool, dgamma, dbeta, add=None, add2=None, sums=None):
     """g = dL/d(act(GN(x))) -> dL/dx (+ add + add2: other pending branches of x's gradient, views allowed); dgamma/dbeta (fp32) are
-    accumulated in place.  sums: a ZEROED fp64 buffer of GN_FUSED_REPLICAS * n * c * 2 elements (engine.Ctx.zeros64) selects the two-launch form
+    accumulated in place.  sums: a ZEROED fp64 buffer of GN_FUSED_REPLICAS * n * c * 2 elements selects the two-launch form
     (mi_gn_bwd_fused: atomics instead of the finalize launch)."""
     if add is None and add2 is not None:
         add, add2 = add2, None
