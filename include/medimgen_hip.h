@@ -354,6 +354,24 @@ int mi_axpy_f32(float* y, const float* x, float alpha, int64_t n, hipStream_t st
 /* x *= alpha: `latents * inferer.scale_factor` of the latent-diffusion step (train_ldm.py:157) */
 int mi_scale_f32(float* x, float alpha, int64_t n, hipStream_t stream);
 
+/* ---- validation passes (LDM.validate_epoch T-LDM:193-239; AutoEncoder.validate_one_epoch T-AE:438-467; adapt_kl_loss_weight
+ * T-AE:295-328): forward-only loss values, the epoch's running mean kept on the device.
+ * `acc` is a meter block of MI_METER_HEADER + MI_METER_PARTIALS doubles, 8-byte aligned, the size the bytes query below returns:
+ *   acc[0] loss of the last batch, acc[1] running sum of the batch losses, acc[2] number of batches, acc[3] reserved,
+ *   acc[MI_METER_HEADER ...] one partial per workgroup (scratch of the call in flight).
+ * Every *_eval call writes acc[0], adds it to acc[1] and adds 1 to acc[2]; the partials are folded in a fixed order in fp64 (no
+ * float atomics), so equal inputs give bit-identical blocks.  Calls on one block must be stream-ordered.
+ *   mse / l1: pred channels-last bf16 [N][V][C] (dense), target fp32 NC[D]HW: mean over all N*C*V elements of (pred - target)^2
+ *             / |pred - target| -- the value the fwd_bwd entry points of the train step put in *loss, no gradient tensor written.
+ *   kl:       0.5 * sum(mu^2 + sigma^2 - log(sigma^2) - 1) / N over channels-last bf16 mu / sigma (get_kl_loss, T-AE:68-72); no z. */
+#define MI_METER_HEADER 4
+#define MI_METER_PARTIALS 1024
+int64_t mi_meter_bytes(void);
+int mi_meter_reset(double* acc, hipStream_t stream);
+int mi_mse_eval(const void* pred, const float* target, double* acc, int N, int C, int64_t V, hipStream_t stream);
+int mi_l1_eval(const void* pred, const float* target, double* acc, int N, int C, int64_t V, hipStream_t stream);
+int mi_kl_eval(const void* mu, const void* sigma, double* acc, int N, int C, int64_t V, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,15 +112,20 @@ _SIGS = {
     "mi_adam_step_dev": [_p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
     "mi_axpy_f32": [_p, _p, _f, _l, _p],
     "mi_scale_f32": [_p, _f, _l, _p],
+    "mi_meter_bytes": [],
+    "mi_meter_reset": [_p, _p],
+    "mi_mse_eval": [_p, _p, _p, _i, _i, _l, _p],
+    "mi_l1_eval": [_p, _p, _p, _i, _i, _l, _p],
+    "mi_kl_eval": [_p, _p, _p, _i, _i, _l, _p],
 }
-_RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l}
-_NOCHECK = {"mi_abi_version", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks"}
+_RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l}
+_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks"}
 
 _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 11
+ABI_VERSION = 12
 
 
 def exported_symbols() -> list[str]:

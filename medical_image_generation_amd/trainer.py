@@ -13,9 +13,17 @@ torch autograd on the reconstruction: those networks are third-party torch modul
 
 Data parallelism: one process per GPU; the trainable prefix of the flat gradient arena is all-reduced
 (average) over RCCL in a few large buckets -- statically unused `proj_attn.*` tensors live outside that prefix.
+
+Validation (the loop that ends every epoch of the reference and decides `best_model.pth`: LDM.validate_epoch, train_ldm.py:193-239;
+AutoEncoder.validate_one_epoch, train_autoencoder.py:438-467; adapt_kl_loss_weight, train_autoencoder.py:295-328): every trainer has
+`validate()` / `capture_validate()` / `validate_graph()` -- the same forward without a tape, a forward-only loss reduction, and a
+`ValidationMeter` that keeps the epoch's running mean on the device, so a validation epoch costs ONE host synchronisation
+(`meter.mean()`, the number checkpoint.save_model takes as `validation_loss`: train_ldm.py:466-491, train_autoencoder.py:533-564).
+Nothing the train step owns is written.
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -24,10 +32,65 @@ import torch.distributed as dist
 from . import ddp
 from . import engine as E
 from . import hipops as ops
-from ._lib import call, ptr
+from ._lib import call, call_raw, ptr
 from .optim import FusedAdam
 
 F32 = torch.float32
+METER_HEADER = 4  # include/medimgen_hip.h MI_METER_HEADER: {last batch loss, sum of batch losses, batch count, reserved}
+
+
+class ValidationMeter:
+    """Running mean of the per-batch validation losses, on the device: the `np.mean(losses)` of the reference's validation loops
+    (train_ldm.py:231-239, train_autoencoder.py:458-461, 316-318) without a `.item()` per batch.
+
+    `acc` is the fp64 block the mi_*_eval kernels update: acc[0] the last batch's loss, acc[1] the sum of the batch losses, acc[2] the
+    number of batches (then the kernels' per-workgroup partials).  `last` is a device scalar (a view: the next batch overwrites it);
+    `mean()` synchronises ONCE and returns a Python float.  With a process group of more than one rank, {sum, count} are all-reduced
+    (SUM) first, so every rank gets the global mean -- ranks may have seen different numbers of batches.  On a CPU device only the
+    reduction part works (`add()` stands in for the kernels): that is what the gloo tests drive."""
+
+    def __init__(self, device, process_group=None):
+        self.device = torch.device(device)
+        self.pg = process_group
+        n = call_raw("mi_meter_bytes") // 8 if self.device.type == "cuda" else METER_HEADER
+        self.acc = torch.zeros(n, dtype=torch.float64, device=self.device)
+
+    def reset(self):
+        if self.acc.is_cuda:
+            call("mi_meter_reset", ptr(self.acc))  # a kernel, like every write the captured graphs are ordered against
+        else:
+            self.acc[:METER_HEADER].zero_()
+
+    def add(self, loss):
+        """Account one batch loss computed elsewhere (a Python float or a tensor on the meter's device); no synchronisation."""
+        loss = torch.as_tensor(loss, dtype=torch.float64, device=self.device).reshape(())
+        self.acc[0] = loss
+        self.acc[1] += loss
+        self.acc[2] += 1.0
+
+    @property
+    def last(self):
+        return self.acc[0]
+
+    def mean(self) -> float:
+        sc = self.acc[1:3]
+        world = dist.get_world_size(self.pg) if (self.pg is not None or dist.is_initialized()) else 1
+        if world > 1:
+            sc = sc.clone()
+            dist.all_reduce(sc, op=dist.ReduceOp.SUM, group=self.pg)
+        total, count = sc.tolist()  # the one host synchronisation
+        if count == 0:
+            raise ValueError("ValidationMeter.mean(): no batch has been accounted since reset()")
+        return total / count
+
+
+def kl_weight_from_mean(kl_mean: float) -> float:
+    """The decade rule of adapt_kl_loss_weight (train_autoencoder.py:319-327): kl_weight = 0.001 / 10 ** floor(log10(mean KL)), i.e.
+    the weight that brings the KL term to the order of 1e-3 (3.7e3 -> 1e-6, 0.42 -> 1e-2, 1.0 -> 1e-3)."""
+    kl_mean = float(kl_mean)
+    if not kl_mean > 0 or math.isinf(kl_mean):
+        raise ValueError(f"the mean KL must be positive and finite, got {kl_mean}")
+    return 0.001 / 10.0 ** math.floor(math.log10(kl_mean))
 
 
 class DDPMSchedule:
@@ -97,6 +160,8 @@ class _ArenaTrainer:
         self._static = None
         self._force_split = False  # tests: capture the two-graph form with world 1
         self._force_exchange = False  # tests: issue the (one-rank) collectives although world == 1
+        self._val_meter = None   # the meter validate() uses when none is given
+        self._val = None         # capture_validate(): (graph, static inputs, meter, outputs, pinned objects)
         self.overlap = (os.environ.get("MI_DDP_OVERLAP", "1") != "0") if overlap is None else bool(overlap)
 
     # ------------------------------------------------------------------ hyperparameters (self.optimizer's group)
@@ -241,10 +306,75 @@ class _ArenaTrainer:
         # split slabs), the GroupNorm workspace and the arena.  Pin them for as long as the graphs exist -- a forward at another
         # shape between train steps (validation, DiffusionInferer.sample) replaces model._packb / grows the workspace, and their
         # destructors would hipFree memory the next replay still writes to.
-        self._pinned = [(m._packb, dict(m._plans), m._arena) for m in self._models()] + [dict(ops._ws_cache)]
+        self._pinned = self._pin_state()
+
+    def _pin_state(self):
+        return [(m._packb, dict(m._plans), m._arena) for m in self._models()] + [dict(ops._ws_cache)]
 
     def _models(self):
         return [self.model]
+
+    # ------------------------------------------------------------------ validation (T-LDM:193-239, T-AE:438-467, 295-328)
+    def _eval_forward(self, meter, *inputs, **options):
+        """The no-grad forward of one validation batch and its loss into `meter` (subclasses); returns extra outputs or None."""
+        raise NotImplementedError
+
+    def _meter(self, meter):
+        if meter is None:
+            if self._val_meter is None:
+                self._val_meter = ValidationMeter(self.device, self.pg)
+            meter = self._val_meter
+        if not isinstance(meter, ValidationMeter) or meter.acc.device.type != self.device.type:
+            raise ValueError("meter must be a ValidationMeter on the trainer's device")
+        return meter
+
+    def validate(self, *inputs, meter=None, **options):
+        """One validation batch, eager and tape-less; the batch loss goes into `meter` (default: the trainer's own) and is returned as a
+        device scalar (`meter.last`: fp64, overwritten by the next batch) without synchronising.  Takes step()'s inputs.  Writes nothing
+        the train step owns: parameters, gradients, pending micro-step sums, moments, step count and `loss` stay bit-identical."""
+        meter = self._meter(meter)
+        extra = self._eval_forward(meter, *inputs, **options)
+        return meter.last if extra is None else (meter.last, extra)
+
+    def capture_validate(self, *inputs, warmup=1, meter=None, **options):
+        """Capture validate() as ONE hipGraph around static copies of `inputs` -- independent of capture(): own graph, own memory pool,
+        any batch size or patch shape.  The weight packing is inside the graph (the parameters change between epochs).  `meter` (default:
+        the trainer's own) is a static pointer of the graph.  The warm-up passes (they create the conv plans and workspaces of this
+        shape outside the capture) run on a scratch meter, so `meter` is not touched before the first validate_graph()."""
+        meter = self._meter(meter)
+        scratch = {k: (ValidationMeter(self.device) if isinstance(v, ValidationMeter) else v) for k, v in options.items()}
+        static = tuple(None if t is None else t.clone() for t in inputs)
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(max(1, warmup)):
+                self._eval_forward(ValidationMeter(self.device), *static, **scratch)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            extra = self._eval_forward(meter, *static, **options)
+        # the pinning rule of capture(), in both directions: this graph keeps what it points at alive (so a later capture() / step at
+        # another shape may replace the model's PackBatch or grow the workspace), and capture() keeps its own set (so this capture may)
+        self._val = (g, static, meter, extra, self._pin_state() + [options])
+
+    def validate_graph(self, *inputs, meter=None):
+        """Replay; inputs given (positionally, None = keep) are copied into the static buffers first.  `meter`, when given, must be the
+        one the graph was captured with.  Returns what validate() returns (extra outputs live in static buffers of the graph)."""
+        if self._val is None:
+            raise RuntimeError("call capture_validate() first")
+        g, static, captured, extra, _ = self._val
+        if meter is not None and meter is not captured:
+            raise ValueError("validate_graph() accounts into the meter given to capture_validate(): its block is a static pointer of the graph")
+        if self.model._arena is not self.arena:
+            raise RuntimeError("the model's parameter arena was rebuilt after capture_validate(): capture again")
+        for buf, t in zip(static, inputs):
+            if t is not None:
+                if buf is None:
+                    raise ValueError("this input was None at capture_validate(): capture again with a tensor in its place")
+                buf.copy_(t)
+        g.replay()
+        return captured.last if extra is None else (captured.last, extra)
 
     def step_graph(self, *inputs):
         """Replay; inputs given (positionally, None = keep) are copied into the static buffers first."""
@@ -285,13 +415,9 @@ class DDPMTrainer(_ArenaTrainer):
                          grad_accumulate_step, overlap)
         self.schedule = schedule or DDPMSchedule(device=self.device)
 
-    def _forward(self, x0, noise, timesteps, class_labels=None, context=None, condition=None):
-        """q-sample -> UNet -> MSE (+ its gradient).  x0/noise: fp32 NCDHW, timesteps: int64 [N]; class_labels: int64 [N], only for
-        a net built with num_class_embeds; context: fp32 [N, tokens, cross_attention_dim], only for with_conditioning=True;
-        condition: fp32 NC'[D]HW concatenated un-noised behind the noised channels (mode="concat")."""
+    def _check_inputs(self, x0, noise, timesteps, class_labels, context, condition):
+        """Raw pointers go to the kernels: refuse anything they would misread instead of reading out of bounds.  -> channels of `condition`."""
         m = self.model
-        a = self.arena
-        # raw pointers go to the kernels: refuse anything they would misread instead of reading out of bounds
         if not (x0.is_cuda and noise.is_cuda and timesteps.is_cuda):
             raise RuntimeError("DDPMTrainer inputs must live on the GPU")
         if x0.dtype != F32 or noise.dtype != F32 or not x0.is_contiguous() or not noise.is_contiguous() or x0.shape != noise.shape:
@@ -310,7 +436,20 @@ class DDPMTrainer(_ArenaTrainer):
             raise ValueError(f"the model predicts {m.out_channels} channels but the noised input has {x0.shape[1]}: the loss target "
                              "(the noise / velocity of x0) must have the prediction's channel count; un-noised conditioning channels go in "
                              "`condition=`")
-        a.grad.zero_()
+        if (class_labels is None) != (getattr(m, "num_class_embeds", None) is None):
+            raise ValueError("class_labels should be provided exactly when the model has num_class_embeds")
+        if (context is not None) != bool(getattr(m, "with_conditioning", False)):
+            raise ValueError("context should be provided exactly when the model has with_conditioning = True")
+        if context is not None:
+            if not context.is_cuda or context.dtype != F32 or context.dim() != 3 or context.shape[0] != x0.shape[0] or \
+                    context.shape[2] != m.cross_attention_dim:
+                raise ValueError(f"context must be a GPU fp32 tensor [batch, tokens, {m.cross_attention_dim}]")
+        return cc
+
+    def _predict(self, grad_enabled, x0, noise, timesteps, class_labels, context, condition, cc):
+        """q-sample -> UNet.  -> (ctx, pred, target, (n, v), the tensors its kernels read); target: the noise, or the velocity mi_qsample
+        wrote (v-prediction)."""
+        m = self.model
         sd = m.spatial_dims
         n, c = x0.shape[0], x0.shape[1]
         sp = tuple(x0.shape[2:])
@@ -323,23 +462,33 @@ class DDPMTrainer(_ArenaTrainer):
         target = torch.empty_like(noise) if vpred else noise
         call("mi_qsample", ptr(x0), ptr(noise), ptr(self.schedule.sqrt_acp), ptr(self.schedule.sqrt_1macp), ptr(timesteps), ptr(condition), cc,
              ptr(x_t), ptr(target) if vpred else None, n, c, v, self.schedule.num_train_timesteps)
-        ctx = E.Ctx(a, m._plans, grad_enabled=True, prepacked=m.pack_all())
-        if (class_labels is None) != (getattr(m, "num_class_embeds", None) is None):
-            raise ValueError("class_labels should be provided exactly when the model has num_class_embeds")
+        ctx = E.Ctx(self.arena, m._plans, grad_enabled=grad_enabled, prepacked=m.pack_all())
         ctx_tokens = None
-        if (context is not None) != bool(getattr(m, "with_conditioning", False)):
-            raise ValueError("context should be provided exactly when the model has with_conditioning = True")
         if context is not None:
-            if not context.is_cuda or context.dtype != F32 or context.dim() != 3 or context.shape[0] != n or context.shape[2] != m.cross_attention_dim:
-                raise ValueError(f"context must be a GPU fp32 tensor [batch, tokens, {m.cross_attention_dim}]")
             ctx_tokens = ops.cast_bf16(context.contiguous().reshape(-1, context.shape[2]))
         pred = m._run(ctx, x_t, timesteps, need_dx=False, class_labels=class_labels, context=ctx_tokens)
-        dpred = torch.empty_like(pred)
         if pred.shape[-1] != target.shape[1]:  # k_mse indexes both with ONE channel count
             raise ValueError(f"prediction has {pred.shape[-1]} channels, the target {target.shape[1]}")
+        return ctx, pred, target, (n, v), (x_t, target, ctx_tokens, condition)
+
+    def _forward(self, x0, noise, timesteps, class_labels=None, context=None, condition=None):
+        """q-sample -> UNet -> MSE (+ its gradient).  x0/noise: fp32 NCDHW, timesteps: int64 [N]; class_labels: int64 [N], only for
+        a net built with num_class_embeds; context: fp32 [N, tokens, cross_attention_dim], only for with_conditioning=True;
+        condition: fp32 NC'[D]HW concatenated un-noised behind the noised channels (mode="concat")."""
+        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition)
+        self.arena.grad.zero_()
+        ctx, pred, target, (n, v), keep = self._predict(True, x0, noise, timesteps, class_labels, context, condition, cc)
+        dpred = torch.empty_like(pred)
         call("mi_mse_fwd_bwd", ptr(pred), ptr(target), ptr(dpred), ptr(self.loss), n, pred.shape[-1], v, 1.0)
-        self._keep = (x_t, target, ctx_tokens, condition)  # read by kernels still in flight / by the second graph of a split capture
+        self._keep = keep  # read by kernels still in flight / by the second graph of a split capture
         return ctx.tape, pred, dpred
+
+    def _eval_forward(self, meter, x0, noise, timesteps, class_labels=None, context=None, condition=None):
+        """LDM.validate_epoch's batch (T-LDM:206-229): q-sample -> UNet -> mse_loss against the noise / velocity; _forward's inputs and
+        checks, no tape, no gradient tensor."""
+        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition)
+        _, pred, target, (n, v), _ = self._predict(False, x0, noise, timesteps, class_labels, context, condition, cc)
+        call("mi_mse_eval", ptr(pred), ptr(target), ptr(meter.acc), n, pred.shape[-1], v)
 
 
 class LDMTrainer(DDPMTrainer):
@@ -392,6 +541,14 @@ class LDMTrainer(DDPMTrainer):
         z = self._latents(images, eps)
         call("mi_scale_f32", ptr(z), self.scale_factor, z.numel())  # latents_scaled = latents * inferer.scale_factor (T-LDM:157)
         return super()._forward(z, noise, timesteps, class_labels, context, condition)
+
+    def _eval_forward(self, meter, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
+        """T-LDM:206-229: latents = autoencoder.encode_stage_2_inputs(images) * scale_factor, then the diffusion batch above."""
+        if self.scale_factor is None:
+            raise RuntimeError("scale_factor is not set: pass it or call estimate_scale_factor(first_batch, eps) (train_ldm.py:110-112)")
+        z = self._latents(images, eps)
+        call("mi_scale_f32", ptr(z), self.scale_factor, z.numel())
+        return super()._eval_forward(meter, z, noise, timesteps, class_labels, context, condition)
 
 
 class AETrainer(_ArenaTrainer):
@@ -509,6 +666,41 @@ class AETrainer(_ArenaTrainer):
             drecon = ops.add(drecon, ops.to_channels_last(g))
             self.reconstruction = rec.detach()
         return tape, recon, drecon
+
+
+    def _eval_forward(self, meter, images, eps, return_recon=False, kl_meter=None):
+        """AutoEncoder.validate_one_epoch's batch (T-AE:447-456): reconstructions, *_ = autoencoder(images) -> l1_loss, and nothing else
+        (no KL, perceptual or adversarial term; the discriminator is not run).  AutoencoderKL.forward samples z = mu + eps * sigma in
+        eval mode too (AEKL:821-825).  kl_meter: a second ValidationMeter that accounts get_kl_loss(z_mu, z_sigma) of the same batch (the
+        loop of adapt_kl_loss_weight, T-AE:295-318).  return_recon: -> the reconstruction as fp32 NC[D]HW (T-AE:463-467: the image pair
+        of the epoch's plots)."""
+        m = self.model
+        if not (images.is_cuda and eps.is_cuda):
+            raise RuntimeError("AETrainer inputs must live on the GPU")
+        if images.dtype != F32 or not images.is_contiguous() or eps.dtype != F32 or not eps.is_contiguous():
+            raise ValueError("images and eps must be contiguous fp32 GPU tensors")
+        if images.dim() != m.spatial_dims + 2 or images.shape[1] != m.in_channels:
+            raise ValueError(f"images must be NC[D]HW with {m.in_channels} channels, got {tuple(images.shape)}")
+        if kl_meter is not None and (kl_meter is meter or self._meter(kl_meter) is not kl_meter):
+            raise ValueError("kl_meter must be a ValidationMeter of its own")
+        n = images.shape[0]
+        v = images.numel() // (n * images.shape[1])
+        x_cl = ops.to_channels_last(images)
+        ctx = E.Ctx(self.arena, m._plans, grad_enabled=False, prepacked=m.pack_all())
+        mu, sigma = m._encode_run(ctx, x_cl, need_dx=False)
+        lc = mu.shape[-1]
+        lv = mu.numel() // (n * lc)
+        if tuple(eps.shape) != (n, lc) + tuple(mu.shape[1:4])[3 - m.spatial_dims:]:
+            raise ValueError(f"eps must have the latent shape, got {tuple(eps.shape)}")
+        z = torch.empty_like(mu)
+        call("mi_reparam_kl_fwd", ptr(mu), ptr(sigma), ptr(eps), ptr(z), None, n, lc, lv, 0.0)
+        if kl_meter is not None:
+            call("mi_kl_eval", ptr(mu), ptr(sigma), ptr(kl_meter.acc), n, lc, lv)
+        recon = m._decode_run(ctx, z, False)
+        if recon.shape[-1] != images.shape[1] or recon.numel() != images.numel():
+            raise ValueError(f"the reconstruction has shape {tuple(recon.shape)} (channels-last) for images {tuple(images.shape)}")
+        call("mi_l1_eval", ptr(recon), ptr(images), ptr(meter.acc), n, recon.shape[-1], v)
+        return ops.to_channels_first(recon, m.spatial_dims) if return_recon else None
 
 
 class AEGANTrainer(AETrainer):
