@@ -22,6 +22,15 @@ from ._lib import call, ptr
 F32 = torch.float32
 
 
+def betas(schedule, num_train_timesteps, beta_start, beta_end):
+    """The fp32 betas of generative's schedulers, for training (trainer.DDPMSchedule) and sampling (DDPMScheduler) alike."""
+    if schedule == "scaled_linear_beta":
+        return torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=F32) ** 2
+    if schedule == "linear_beta":
+        return torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=F32)
+    raise ValueError(f"unknown schedule {schedule}")
+
+
 class DDPMScheduler:
     """`generative.networks.schedulers.DDPMScheduler` as train_ldm.py:74 constructs it (variance_type "fixed_small")."""
 
@@ -31,17 +40,11 @@ class DDPMScheduler:
             raise NotImplementedError("only variance_type='fixed_small' (the upstream default the reference uses)")
         if prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"unknown prediction_type {prediction_type}")
-        if schedule == "scaled_linear_beta":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=F32) ** 2
-        elif schedule == "linear_beta":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=F32)
-        else:
-            raise ValueError(f"unknown schedule {schedule}")
+        self.betas = betas(schedule, num_train_timesteps, beta_start, beta_end)
         self.num_train_timesteps, self.prediction_type, self.clip_sample = num_train_timesteps, prediction_type, clip_sample
-        self.betas = betas
-        self.alphas = 1.0 - betas
+        self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        acp, b = self.alphas_cumprod.double(), betas.double()
+        acp, b = self.alphas_cumprod.double(), self.betas.double()
         prev = torch.cat([torch.ones(1, dtype=torch.float64), acp[:-1]])
         sigma = ((1 - prev) / (1 - acp) * b).clamp(min=1e-20).sqrt()
         sigma[0] = 0.0  # no noise is added at t = 0

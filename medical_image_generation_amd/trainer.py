@@ -32,6 +32,7 @@ import torch.distributed as dist
 from . import ddp
 from . import engine as E
 from . import hipops as ops
+from . import inferer
 from ._lib import call, call_raw, ptr
 from .optim import FusedAdam
 
@@ -98,12 +99,7 @@ class DDPMSchedule:
 
     def __init__(self, num_train_timesteps=1000, schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205,
                  prediction_type="epsilon", device="cuda"):
-        if schedule == "scaled_linear_beta":
-            betas = torch.linspace(beta_start ** 0.5, beta_end ** 0.5, num_train_timesteps, dtype=F32) ** 2
-        elif schedule == "linear_beta":
-            betas = torch.linspace(beta_start, beta_end, num_train_timesteps, dtype=F32)
-        else:
-            raise ValueError(f"unknown schedule {schedule}")
+        betas = inferer.betas(schedule, num_train_timesteps, beta_start, beta_end)
         if prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"unknown prediction_type {prediction_type} (train_ldm.py:163-166 knows 'epsilon' and 'v_prediction')")
         acp = torch.cumprod(1.0 - betas, dim=0)
@@ -275,14 +271,9 @@ class _ArenaTrainer:
         inside a capture: the all-reduces are issued between the replays, the early segment's concurrently with the second graph."""
         if self.grad_accumulate_step != 1:
             raise RuntimeError("hipGraph capture covers grad_accumulate_step == 1; use step() for accumulation")
-        self._static = tuple(None if t is None else t.clone() for t in inputs)  # (None: an optional input that is not used)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(warmup):  # creates conv plans / workspaces (hipMalloc) outside capture
-                self.forward_backward(*self._static)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        static = tuple(None if t is None else t.clone() for t in inputs)  # (None: an optional input that is not used)
+        self._warm_up(lambda: self.forward_backward(*static), warmup)
+        self._static = static  # (bound once the warm-up has accepted the inputs: a refused capture() leaves an earlier one intact)
         split = self.overlap and (self.world > 1 or self._force_split) and 0 < self.arena.n_late < self.arena.n_trainable
         # thread_local: a collective library's watchdog thread polling events must not invalidate the capture
         self._g_fb, self._g_fb2 = torch.cuda.CUDAGraph(), None
@@ -307,6 +298,27 @@ class _ArenaTrainer:
         # shape between train steps (validation, DiffusionInferer.sample) replaces model._packb / grows the workspace, and their
         # destructors would hipFree memory the next replay still writes to.
         self._pinned = self._pin_state()
+
+    @staticmethod
+    def _warm_up(fn, passes):
+        """`passes` runs of fn() on a side stream before a capture: they create the conv plans / workspaces (hipMalloc) outside it."""
+        s = torch.cuda.Stream()
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(passes):
+                fn()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+
+    def _load_static(self, static, inputs, where, remedy="capture again"):
+        """Before a replay of the graphs captured by `where`: inputs given (None = keep) are copied into their static buffers."""
+        if self.model._arena is not self.arena:  # .to() / .cuda() / load into new storage: the graphs point at the old buffers
+            raise RuntimeError(f"the model's parameter arena was rebuilt after {where}: {remedy}")
+        for buf, t in zip(static, inputs):
+            if t is not None:
+                if buf is None:
+                    raise ValueError(f"this input was None at {where}: capture again with a tensor in its place")
+                buf.copy_(t)
 
     def _pin_state(self):
         return [(m._packb, dict(m._plans), m._arena) for m in self._models()] + [dict(ops._ws_cache)]
@@ -344,13 +356,7 @@ class _ArenaTrainer:
         meter = self._meter(meter)
         scratch = {k: (ValidationMeter(self.device) if isinstance(v, ValidationMeter) else v) for k, v in options.items()}
         static = tuple(None if t is None else t.clone() for t in inputs)
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(max(1, warmup)):
-                self._eval_forward(ValidationMeter(self.device), *static, **scratch)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        self._warm_up(lambda: self._eval_forward(ValidationMeter(self.device), *static, **scratch), max(1, warmup))
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
             extra = self._eval_forward(meter, *static, **options)
@@ -366,26 +372,14 @@ class _ArenaTrainer:
         g, static, captured, extra, _ = self._val
         if meter is not None and meter is not captured:
             raise ValueError("validate_graph() accounts into the meter given to capture_validate(): its block is a static pointer of the graph")
-        if self.model._arena is not self.arena:
-            raise RuntimeError("the model's parameter arena was rebuilt after capture_validate(): capture again")
-        for buf, t in zip(static, inputs):
-            if t is not None:
-                if buf is None:
-                    raise ValueError("this input was None at capture_validate(): capture again with a tensor in its place")
-                buf.copy_(t)
+        self._load_static(static, inputs, "capture_validate()")
         g.replay()
         return captured.last if extra is None else (captured.last, extra)
 
     def step_graph(self, *inputs):
         """Replay; inputs given (positionally, None = keep) are copied into the static buffers first."""
         assert self._graph, "call capture() first"
-        if self.model._arena is not self.arena:  # .to() / .cuda() / load into new storage: the graphs point at the old buffers
-            raise RuntimeError("the model's parameter arena was rebuilt after capture(): create a new trainer (or call capture() again)")
-        for buf, t in zip(self._static, inputs):
-            if t is not None:
-                if buf is None:
-                    raise ValueError("this input was None at capture(): capture again with a tensor in its place")
-                buf.copy_(t)
+        self._load_static(self._static, inputs, "capture()", "create a new trainer (or call capture() again)")
         ex = self._exchange() if self._exchanging() else None
         self._g_fb.replay()
         if self._g_fb2 is not None:
@@ -453,9 +447,7 @@ class DDPMTrainer(_ArenaTrainer):
         sd = m.spatial_dims
         n, c = x0.shape[0], x0.shape[1]
         sp = tuple(x0.shape[2:])
-        v = 1
-        for s in sp:
-            v *= s
+        v = math.prod(sp)
         dims = (1,) * (3 - sd) + sp
         x_t = torch.empty((n,) + dims + (c + cc,), dtype=torch.bfloat16, device=x0.device)
         vpred = self.schedule.prediction_type == "v_prediction"  # target = scheduler.get_velocity(x0, noise, t), T-LDM:163-165
@@ -491,6 +483,31 @@ class DDPMTrainer(_ArenaTrainer):
         call("mi_mse_eval", ptr(pred), ptr(target), ptr(meter.acc), n, pred.shape[-1], v)
 
 
+def _encode_sample(ae, arena, images, eps, grad_enabled, loss, kl_weight):
+    """encode -> z = z_mu + eps * z_sigma (AEKL:786-787), channels-last: the head of the autoencoder's train step, of its validation
+    batch and of the latent-diffusion trainer's frozen encoder.  Raw pointers go to the kernels: refuse anything they would misread
+    instead of reading out of bounds (tensor metadata only: no synchronisation).  `loss`: the device scalar that is reset and then
+    receives kl_weight * KL, or None -- reset only here, so a refused call leaves the last step's loss standing.  -> (ctx, x_cl, mu, sigma, z, (n, latent channels, latent voxels))."""
+    if not (images.is_cuda and eps.is_cuda):
+        raise RuntimeError("AETrainer inputs must live on the GPU")
+    if images.dtype != F32 or not images.is_contiguous() or eps.dtype != F32 or not eps.is_contiguous():
+        raise ValueError("images and eps must be contiguous fp32 GPU tensors")
+    if images.dim() != ae.spatial_dims + 2 or images.shape[1] != ae.in_channels:
+        raise ValueError(f"images must be NC[D]HW with {ae.in_channels} channels, got {tuple(images.shape)}")
+    x_cl = ops.to_channels_last(images)
+    ctx = E.Ctx(arena, ae._plans, grad_enabled=grad_enabled, prepacked=ae.pack_all())
+    mu, sigma = ae._encode_run(ctx, x_cl, need_dx=False)
+    n, lc = mu.shape[0], mu.shape[-1]
+    lv = mu.numel() // (n * lc)
+    if tuple(eps.shape) != (n, lc) + tuple(mu.shape[1:4])[3 - ae.spatial_dims:]:
+        raise ValueError(f"eps must have the latent shape, got {tuple(eps.shape)}")
+    if loss is not None:
+        loss.zero_()
+    z = torch.empty_like(mu)
+    call("mi_reparam_kl_fwd", ptr(mu), ptr(sigma), ptr(eps), ptr(z), ptr(loss), n, lc, lv, kl_weight)
+    return ctx, x_cl, mu, sigma, z, (n, lc, lv)
+
+
 class LDMTrainer(DDPMTrainer):
     """The latent-diffusion train step as train_ldm.LDM.train_one_epoch runs it (T-LDM:145-180, 'vae' branch):
 
@@ -513,19 +530,10 @@ class LDMTrainer(DDPMTrainer):
 
     def _latents(self, images, eps):
         """encode_stage_2_inputs (AEKL:827-830): z = z_mu + eps * z_sigma, fp32 NC[D]HW, unscaled; no tape."""
-        ae = self.autoencoder
-        if images.dtype != F32 or not images.is_cuda or not images.is_contiguous() or eps.dtype != F32 or not eps.is_contiguous():
+        if not (images.is_cuda and eps.is_cuda):  # (this trainer's wording; every other refusal is _encode_sample's)
             raise ValueError("images and eps must be contiguous fp32 GPU tensors")
-        x_cl = ops.to_channels_last(images)
-        ctx = E.Ctx(self.ae_arena, ae._plans, grad_enabled=False, prepacked=ae.pack_all())
-        mu, sigma = ae._encode_run(ctx, x_cl, need_dx=False)
-        n, lc = mu.shape[0], mu.shape[-1]
-        lv = mu.numel() // (n * lc)
-        if tuple(eps.shape) != (n, lc) + tuple(d for d in mu.shape[1:4])[3 - ae.spatial_dims:]:
-            raise ValueError(f"eps must have the latent shape, got {tuple(eps.shape)}")
-        z = torch.empty_like(mu)
-        call("mi_reparam_kl_fwd", ptr(mu), ptr(sigma), ptr(eps), ptr(z), None, n, lc, lv, 0.0)
-        return ops.to_channels_first(z, ae.spatial_dims)
+        z = _encode_sample(self.autoencoder, self.ae_arena, images, eps, False, None, 0.0)[4]
+        return ops.to_channels_first(z, self.autoencoder.spatial_dims)
 
     @torch.no_grad()
     def estimate_scale_factor(self, images, eps):
@@ -533,22 +541,22 @@ class LDMTrainer(DDPMTrainer):
         self.scale_factor = float(1.0 / torch.std(self._latents(images, eps)))
         return self.scale_factor
 
-    def _forward(self, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
-        """condition: latent-shaped fp32 tensor (e.g. the label mask resampled to the latent grid) concatenated un-noised behind the
-        scaled latents -- BASELINE configs[4]."""
-        if self.scale_factor is None:
-            raise RuntimeError("scale_factor is not set: pass it or call estimate_scale_factor(first_batch, eps) (train_ldm.py:110-112)")
-        z = self._latents(images, eps)
-        call("mi_scale_f32", ptr(z), self.scale_factor, z.numel())  # latents_scaled = latents * inferer.scale_factor (T-LDM:157)
-        return super()._forward(z, noise, timesteps, class_labels, context, condition)
-
-    def _eval_forward(self, meter, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
-        """T-LDM:206-229: latents = autoencoder.encode_stage_2_inputs(images) * scale_factor, then the diffusion batch above."""
+    def _scaled_latents(self, images, eps):
+        """latents_scaled = autoencoder.encode_stage_2_inputs(images) * inferer.scale_factor (T-LDM:154-157)."""
         if self.scale_factor is None:
             raise RuntimeError("scale_factor is not set: pass it or call estimate_scale_factor(first_batch, eps) (train_ldm.py:110-112)")
         z = self._latents(images, eps)
         call("mi_scale_f32", ptr(z), self.scale_factor, z.numel())
-        return super()._eval_forward(meter, z, noise, timesteps, class_labels, context, condition)
+        return z
+
+    def _forward(self, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
+        """condition: latent-shaped fp32 tensor (e.g. the label mask resampled to the latent grid) concatenated un-noised behind the
+        scaled latents -- BASELINE configs[4]."""
+        return super()._forward(self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition)
+
+    def _eval_forward(self, meter, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
+        """T-LDM:206-229: latents = autoencoder.encode_stage_2_inputs(images) * scale_factor, then the diffusion batch above."""
+        return super()._eval_forward(meter, self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition)
 
 
 class AETrainer(_ArenaTrainer):
@@ -625,22 +633,10 @@ class AETrainer(_ArenaTrainer):
         return super().step_graph(images, eps)
 
     def _forward(self, images, eps):
-        m, a = self.model, self.arena
-        a.grad.zero_()
-        self.loss.zero_()
-        n, c = images.shape[0], images.shape[1]
-        sp = tuple(images.shape[2:])
-        v = 1
-        for s in sp:
-            v *= s
-        x_cl = ops.to_channels_last(images)
-        ctx = E.Ctx(a, m._plans, grad_enabled=True, prepacked=m.pack_all())
+        m = self.model
+        ctx, x_cl, mu, sigma, z, (n, lc, lv) = _encode_sample(m, self.arena, images, eps, True, self.loss, self.kl_weight)
+        self.arena.grad.zero_()  # (after the inputs were accepted, before anything is written to it: the forward only records)
         tape = ctx.tape
-        mu, sigma = m._encode_run(ctx, x_cl, need_dx=False)
-        lc = mu.shape[-1]
-        lv = mu.numel() // (n * lc)
-        z = torch.empty_like(mu)
-        call("mi_reparam_kl_fwd", ptr(mu), ptr(sigma), ptr(eps), ptr(z), ptr(self.loss), n, lc, lv, self.kl_weight)
 
         def bwd():
             dz = tape.take(z)
@@ -651,13 +647,13 @@ class AETrainer(_ArenaTrainer):
         tape.record(bwd)
         recon = m._decode_run(ctx, z, True)
         drecon = torch.empty_like(recon)
-        call("mi_l1_fwd_bwd", ptr(recon), ptr(images), ptr(drecon), ptr(self.loss), n, recon.shape[-1], v, 1)
+        call("mi_l1_fwd_bwd", ptr(recon), ptr(images), ptr(drecon), ptr(self.loss), n, recon.shape[-1], math.prod(images.shape[2:]), 1)
         if self.perceptual is not None:
             self.perc_loss.zero_()
             self.perceptual.hip(recon, x_cl, self._perc_idx, self.perc_loss, self.perc_weight, grad=drecon)  # gradient added into drecon
             ops.add_f32_(self.loss.view(1, 1), self.perc_loss.view(1, 1))
         if self.extra_loss is not None:
-            rec = ops.to_channels_first(recon, len(sp)).requires_grad_(True)
+            rec = ops.to_channels_first(recon, m.spatial_dims).requires_grad_(True)
             with torch.enable_grad():
                 extra = self.extra_loss(rec, images)
                 (g,) = torch.autograd.grad(extra, rec)
@@ -667,7 +663,6 @@ class AETrainer(_ArenaTrainer):
             self.reconstruction = rec.detach()
         return tape, recon, drecon
 
-
     def _eval_forward(self, meter, images, eps, return_recon=False, kl_meter=None):
         """AutoEncoder.validate_one_epoch's batch (T-AE:447-456): reconstructions, *_ = autoencoder(images) -> l1_loss, and nothing else
         (no KL, perceptual or adversarial term; the discriminator is not run).  AutoencoderKL.forward samples z = mu + eps * sigma in
@@ -675,31 +670,15 @@ class AETrainer(_ArenaTrainer):
         loop of adapt_kl_loss_weight, T-AE:295-318).  return_recon: -> the reconstruction as fp32 NC[D]HW (T-AE:463-467: the image pair
         of the epoch's plots)."""
         m = self.model
-        if not (images.is_cuda and eps.is_cuda):
-            raise RuntimeError("AETrainer inputs must live on the GPU")
-        if images.dtype != F32 or not images.is_contiguous() or eps.dtype != F32 or not eps.is_contiguous():
-            raise ValueError("images and eps must be contiguous fp32 GPU tensors")
-        if images.dim() != m.spatial_dims + 2 or images.shape[1] != m.in_channels:
-            raise ValueError(f"images must be NC[D]HW with {m.in_channels} channels, got {tuple(images.shape)}")
         if kl_meter is not None and (kl_meter is meter or self._meter(kl_meter) is not kl_meter):
             raise ValueError("kl_meter must be a ValidationMeter of its own")
-        n = images.shape[0]
-        v = images.numel() // (n * images.shape[1])
-        x_cl = ops.to_channels_last(images)
-        ctx = E.Ctx(self.arena, m._plans, grad_enabled=False, prepacked=m.pack_all())
-        mu, sigma = m._encode_run(ctx, x_cl, need_dx=False)
-        lc = mu.shape[-1]
-        lv = mu.numel() // (n * lc)
-        if tuple(eps.shape) != (n, lc) + tuple(mu.shape[1:4])[3 - m.spatial_dims:]:
-            raise ValueError(f"eps must have the latent shape, got {tuple(eps.shape)}")
-        z = torch.empty_like(mu)
-        call("mi_reparam_kl_fwd", ptr(mu), ptr(sigma), ptr(eps), ptr(z), None, n, lc, lv, 0.0)
+        ctx, _, mu, sigma, z, (n, lc, lv) = _encode_sample(m, self.arena, images, eps, False, None, 0.0)
         if kl_meter is not None:
             call("mi_kl_eval", ptr(mu), ptr(sigma), ptr(kl_meter.acc), n, lc, lv)
         recon = m._decode_run(ctx, z, False)
         if recon.shape[-1] != images.shape[1] or recon.numel() != images.numel():
             raise ValueError(f"the reconstruction has shape {tuple(recon.shape)} (channels-last) for images {tuple(images.shape)}")
-        call("mi_l1_eval", ptr(recon), ptr(images), ptr(meter.acc), n, recon.shape[-1], v)
+        call("mi_l1_eval", ptr(recon), ptr(images), ptr(meter.acc), n, recon.shape[-1], math.prod(images.shape[2:]))
         return ops.to_channels_first(recon, m.spatial_dims) if return_recon else None
 
 
@@ -751,9 +730,6 @@ class AEGANTrainer(AETrainer):
         self.optimizer.max_grad_norm = v
         if hasattr(self, "d_optimizer"):
             self.d_optimizer.max_grad_norm = v
-
-    def _models(self):
-        return [self.model]
 
     def _forward(self, images, eps):
         tape, recon, drecon = super()._forward(images, eps)
@@ -814,12 +790,7 @@ class AEGANTrainer(AETrainer):
     def _capture(self, images, eps, warmup, perc_indices):
         super().capture(images, eps, warmup=warmup, perc_indices=perc_indices)
         if self.adversarial:
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                self.d_forward_backward(self._static[0])
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
+            self._warm_up(lambda: self.d_forward_backward(self._static[0]), 1)
             self.d_optimizer.push()
             self._d_clip_captured = self.d_optimizer.clip
             self._g_d = torch.cuda.CUDAGraph()

@@ -611,6 +611,58 @@ def test_graph_survives_other_shape_forward():
     assert bool(torch.isfinite(tra.loss).all())
 
 
+_BAD_AE_INPUTS = {  # (images, eps) from the valid pair -> a pair the kernels would misread, and the refusal it must meet
+    "eps_image_shaped": (lambda x, e: (x, torch.zeros_like(x)), ValueError, "latent shape"),
+    "images_not_contiguous": (lambda x, e: (x.transpose(-1, -2), e), ValueError, "contiguous"),
+    "images_fp64": (lambda x, e: (x.double(), e), ValueError, "fp32"),
+    "images_on_cpu": (lambda x, e: (x.cpu(), e), RuntimeError, "must live on the GPU"),
+    "images_two_channels": (lambda x, e: (torch.cat([x, x], dim=1), e), ValueError, "with 1 channels"),
+}
+
+
+@pytest.mark.parametrize("entry", ["step", "capture", "gan_step"])
+def test_ae_train_path_refuses_what_the_kernels_would_misread(entry):
+    """AETrainer.step / capture and AEGANTrainer.step hand raw pointers to mi_reparam_kl_fwd like validate() does, so they refuse the
+    same inputs with the same errors -- and a refused call leaves parameters, moments, step counts, the pending micro-step count, the
+    last step's loss and its gradients bit-identical, after which a valid step runs."""
+    from medical_image_generation_amd.autoencoderkl import AutoencoderKL
+    from medical_image_generation_amd.discriminator import PatchDiscriminator
+    from medical_image_generation_amd.trainer import AEGANTrainer, AETrainer
+    c = cases.AEKL_CASES["aekl_c3a"]
+    ref = nets.AutoencoderKL(**c["kwargs"])
+    sd = synth.state_dict({k: tuple(v.shape) for k, v in ref.state_dict().items()}, S)
+    ref.load_state_dict(sd)
+    net = AutoencoderKL(**c["kwargs"])
+    net.load_state_dict(sd)
+    x = synth.ellipsoid_volume(S, "x", c["shape"])
+    with torch.no_grad():
+        zshape = tuple(ref.encode(x)[0].shape)
+    x, eps = x.cuda(), synth.tensor(S, "eps0", zshape).cuda()
+    if entry == "gan_step":
+        torch.manual_seed(S)
+        disc = PatchDiscriminator(spatial_dims=3, num_channels=16, in_channels=1, out_channels=1, num_layers_d=3).cuda()
+        tr = AEGANTrainer(net.cuda(), disc, lr=cases.STEP_LR, d_lr=cases.STEP_LR, adversarial=True)
+        state = lambda: [tr.arena.data, tr.exp_avg, tr.exp_avg_sq, tr.step_count, tr.loss, tr.arena.grad,
+                         tr.d_arena.data, tr.d_exp_avg, tr.d_exp_avg_sq, tr.d_step_count]
+    else:
+        tr = AETrainer(net.cuda(), lr=cases.STEP_LR)
+        state = lambda: [tr.arena.data, tr.exp_avg, tr.exp_avg_sq, tr.step_count, tr.loss, tr.arena.grad]
+    tr.step(x, eps)  # moments and step counts are not their initial zeros
+    before, micro = [t.clone() for t in state()], tr._micro
+    refused = tr.capture if entry == "capture" else tr.step
+    for name, (spoil, exc, text) in _BAD_AE_INPUTS.items():
+        with pytest.raises(exc, match=text):
+            refused(*spoil(x, eps))
+        torch.cuda.synchronize()
+        assert tr._micro == micro, name
+        for now, was in zip(state(), before):
+            assert torch.equal(now, was), name
+    loss = tr.step(x, eps)
+    assert bool(torch.isfinite(loss).all())
+    for now, was in zip(state()[:4], before):  # parameters, both moments and the step count moved
+        assert not torch.equal(now, was)
+
+
 def test_ldm_step_matches_oracle_composition():
     """LDMTrainer = the 'vae' branch of train_ldm.py:154-180: no-grad AutoencoderKL.encode_stage_2_inputs -> * scale_factor ->
     q-sample -> UNet -> MSE -> backward, against the same composition of the CPU restatements; scale_factor = 1/std(z) of the first
