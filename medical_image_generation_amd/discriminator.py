@@ -53,8 +53,7 @@ def conv_gemm(ctx: E.Ctx, x, name, k, s, p, bias: bool, need_dx=True, param_grad
             ops.zero_f32_2d_(b8)
             ops.add_f32_(b8[:, :cout], b.view(1, cout))
             b = b8
-    y = torch.empty((n, do, ho, wo, cop), dtype=BF16, device=dev)
-    E._gemm(patches, kk, 0, 0, w2, kk, 0, 0, y, cop, 0, 0, m, cop, kk, 1, 1, bias=b)
+    y = ops.gemm_nt(patches, w2, bias=b).view(n, do, ho, wo, cop)
     ctx.count(2 * m * cout * kk, dgrad=need_dx, wgrad=param_grads)
     if ctx.tape is not None:
         tape = ctx.tape
@@ -68,17 +67,10 @@ def conv_gemm(ctx: E.Ctx, x, name, k, s, p, bias: bool, need_dx=True, param_grad
                 if bias:
                     cs = ops.colsum(dy, merge_batch=True)  # [1, cop]
                     ops.add_f32_(ctx.g(name + ".bias").view(1, cout), cs[:, :cout])
-                mp = _up8(m)  # the GEMM reduces over the voxel axis: pitch rounded up to 8, pad columns zeroed by the transpose kernel
-                dy_t = torch.empty((cop, mp), dtype=BF16, device=dev)
-                p_t = torch.empty((kk, mp), dtype=BF16, device=dev)
-                call("mi_transpose_bf16", ptr(dy), cop, 0, 0, ptr(dy_t), mp, 0, 0, m, cop, 1, 1)
-                call("mi_transpose_bf16", ptr(patches), kk, 0, 0, ptr(p_t), mp, 0, 0, m, kk, 1, 1)
-                dw2 = torch.empty((cop, kk), dtype=F32, device=dev)
-                E._gemm(dy_t, mp, 0, 0, p_t, mp, 0, 0, dw2, kk, 0, 0, cop, kk, mp, 1, 1)
+                dw2 = E.token_wgrad(dy.view(m, cop), patches)  # [cop, kk] fp32, reduced over the voxel axis
                 call("mi_disc_wgrad_unpack", ptr(dw2), ptr(ctx.g(name + ".weight")), cout, cin, taps)
             if need_dx:
-                dpatches = torch.empty((m, kk), dtype=BF16, device=dev)
-                E._gemm(dy, cop, 0, 0, w2t, cop, 0, 0, dpatches, kk, 0, 0, m, kk, cop, 1, 1)
+                dpatches = ops.gemm_nt(dy.view(m, cop), w2t)  # [m, kk]
                 dx = torch.empty((n, d, h, w, cin), dtype=BF16, device=dev)
                 call("mi_col2im3d", ptr(dpatches), ptr(dx), cin, n, d, h, w, cin, k, s, p)
                 tape.put(x, dx)
@@ -220,18 +212,14 @@ def _slice_first(ctx: E.Ctx, x, nc):
     assert nc == 1
     n, d, h, w, c = x.shape
     m = n * d * h * w
-    t = torch.empty((c, m), dtype=BF16, device=x.device)
-    call("mi_transpose_bf16", ptr(x), c, 0, 0, ptr(t), m, 0, 0, m, c, 1, 1)
-    y = t[:1].view(n, d, h, w, 1)
+    y = ops.transpose(x.view(m, c))[:1].view(n, d, h, w, 1)
     if ctx.tape is not None:
         tape = ctx.tape
 
         def bwd():
             g = tape.take(y)
             if g is not None:  # [1, m] -> [m, 8]: the transpose kernel zero-fills the pad columns 1..7
-                back = torch.empty((m, c), dtype=BF16, device=x.device)
-                call("mi_transpose_bf16", ptr(ops.dense(g)), m, 0, 0, ptr(back), c, 0, 0, 1, m, 1, 1)
-                tape.put(x, back.view(x.shape))
+                tape.put(x, ops.transpose(ops.dense(g).view(1, m), pad_to=8).view(x.shape))
 
         tape.record(bwd)
     return y

@@ -509,28 +509,49 @@ def concat(ctx: Ctx, a, b, buf=None):
     return y
 
 
-def _gemm(a, lda, sa1, sa2, b, ldb, sb1, sb2, c, ldc, sc1, sc2, m, n, k, z, z2, alpha=1.0, bias=None, res=None, ldr=0, sr1=0,
-          sr2=0, accumulate=False):
-    """Raw pointer-level NT GEMM: a/b/c/res are (tensor, element_offset) pairs or tensors."""
-
-    def addr(t):
-        if t is None:
-            return None
-        if isinstance(t, tuple):
-            return t[0].data_ptr() + t[1] * t[0].element_size()
-        return t.data_ptr()
-
-    ct = c[0] if isinstance(c, tuple) else c
-    call("mi_gemm_nt_bf16", addr(a), lda, sa1, sa2, addr(b), ldb, sb1, sb2, addr(c), ldc, sc1, sc2, ptr(bias), addr(res), ldr, sr1, sr2,
-         m, n, k, z, z2, float(alpha), int(ct.dtype == F32), int(accumulate))
+def token_wgrad(dy, x, out=None):
+    """dW [N, K] = dy^T x, reduced over the token rows of dy [M, N] and x [M, K] (bf16): both are transposed to a token-last pitch rounded
+    up to 8 (pad columns zeroed by the transpose kernel), then one GEMM runs over it.  out: fp32 view to ACCUMULATE into (else returned)."""
+    return ops.gemm_nt(ops.transpose(dy, pad_to=8), ops.transpose(x, pad_to=8), out=out, out_f32=True, accumulate=out is not None)
 
 
-def _transpose(src, ld_in, si1, si2, rows, cols, z, z2, device):
-    """[z][rows][cols] (strided) -> contiguous [z][cols][rows]."""
-    out = torch.empty((z, cols, rows), dtype=BF16, device=device)
-    a = src[0].data_ptr() + src[1] * 2 if isinstance(src, tuple) else src.data_ptr()
-    call("mi_transpose_bf16", a, ld_in, si1, si2, ptr(out), rows, z2 * cols * rows, cols * rows, rows, cols, z, z2)
-    return out
+def linear_dgrad(dy, wb, out_f32=False):
+    """dx [M, K] = dy [M, N] @ W for the bf16 weight W [N, K]: one transpose of W, one GEMM."""
+    return ops.gemm_nt(dy, ops.transpose(wb), out_f32=out_f32)
+
+
+def _heads(t, b, heads):
+    """[B * S, C] token matrix, a column block of a wider one, or a dense [B, D, H, W, C] activation -> its head views [B, heads, S, hd]."""
+    return t.view(b, -1, heads, t.shape[-1] // heads).permute(0, 2, 1, 3)
+
+
+def _sdpa(q, k, v, scale, out, res=None):
+    """out = softmax(q k^T * scale) v (+ res) per head with materialised fp32 scores (head widths the fused kernels do not take; query and
+    key/value token counts may differ).  q, out, res [B, heads, Sq, hd], k / v [B, heads, Skv, hd]: views (_heads).  Every bf16 matrix whose
+    LAST axis is a token axis is a GEMM operand reduced over that axis: the NT GEMM loads 16-byte pieces along K, so those matrices get
+    a row pitch rounded up to a multiple of 8 with zero pad columns (written by the softmax / transpose kernels themselves) and the
+    products run over the padded K.  (3^3 = 27 or 5^3 = 125 tokens at the coarsest level of non-power-of-two patches.)
+    Returns backward(do, dq, dk, dv), which writes the three gradients into the views it is given."""
+    if q.shape[-1] % 8:
+        raise ValueError("head width must be a multiple of 8 on the HIP path")
+    scores = ops.gemm_nt(q, k, alpha=scale, out_f32=True)                         # [B, heads, Sq, Skv]
+    probs = ops.softmax_fwd(scores, pad8=True)                                    # ... view, pitch Skv rounded up to 8
+    del scores
+    ops.gemm_nt(ops.padded(probs), ops.transpose(v, pad_to=8), out=out, res=res)
+
+    def bwd(do, dq, dk, dv):
+        dp = ops.gemm_nt(do, v, out_f32=True)
+        ds = ops.softmax_bwd(probs, dp, scale)                                    # [B, heads, Sq, Skv] view, padded pitch
+        del dp
+        ops.gemm_nt(ops.padded(ds), ops.transpose(k, pad_to=8), out=dq)
+        qt = ops.transpose(q, pad_to=8)                                           # [B, heads, hd, Sq rounded up to 8]
+        dst = ops.transpose(ds, pad_to=8)                                         # dS^T [B, heads, Skv, ...]
+        ops.gemm_nt(dst, qt, out=dk)
+        del dst, ds
+        pt = ops.transpose(probs, pad_to=8)                                       # P^T
+        ops.gemm_nt(pt, ops.transpose(do, pad_to=8), out=dv)
+
+    return bwd
 
 
 def _attention_flash(ctx, x, name, st, xn, wqkv, qkv, b, s, c, heads, scale):
@@ -565,15 +586,12 @@ def _attention_flash(ctx, x, name, st, xn, wqkv, qkv, b, s, c, heads, scale):
 
 def _attention_param_and_input_grads(ctx, tape, x, name, st, xn, wqkv, dqkv, dy, b, s, c):
     """Shared tail of the attention backward: projection weight/bias gradients, dx through the projections and the norm."""
-    dev = x.device
     pre = name + "." if name else ""
     gw = ctx.arena.span([f"{pre}to_{t}.weight" for t in "qkv"], ctx.arena.grad)
     gb = ctx.arena.span([f"{pre}to_{t}.bias" for t in "qkv"], ctx.arena.grad)
     # dW[3C, C] += dqkv^T xn and db += colsum(dqkv) in ONE pass over the two activations (no transposes, no long-K GEMM on 12 workgroups)
     call("mi_linear_wgrad_bf16", ptr(xn), c, c, ptr(dqkv), 3 * c, 3 * c, b * s, ptr(gw), ptr(gb))
-    wqkv_t = _transpose(wqkv, c, 0, 0, 3 * c, c, 1, 1, dev)[0]           # [C, 3C]
-    dxn = torch.empty(x.shape, dtype=BF16, device=dev)
-    _gemm(dqkv, 3 * c, 0, 0, wqkv_t, 3 * c, 0, 0, dxn, c, 0, 0, b * s, c, 3 * c, 1, 1)
+    dxn = linear_dgrad(dqkv, wqkv).view(x.shape)
     other = tape.take(x)
     dx = ops.gn_bwd(dxn, x, st, ctx.p(pre + "norm.weight"), False, ctx.g(pre + "norm.weight"), ctx.g(pre + "norm.bias"), add=dy, add2=other)
     tape.grads[id(x)] = dx
@@ -585,7 +603,6 @@ def attention(ctx: Ctx, x, name, groups, eps, heads):
     Channels-last makes the reference's [B,C,S]->[B,S,C] transpose free."""
     b, d_, h_, w_, c = x.shape
     s = d_ * h_ * w_
-    hd = c // heads
     scale = 1.0 / math.sqrt(c / heads)
     dev = x.device
     pre = name + "." if name else ""  # stand-alone blocks (blocks.AttentionBlock) have un-prefixed parameter names
@@ -593,33 +610,12 @@ def attention(ctx: Ctx, x, name, groups, eps, heads):
     xn = ops.gn_apply(x, st, False)                                              # [B, S, C]
     wqkv = ops.cast_bf16(ctx.arena.span([f"{pre}to_{t}.weight" for t in "qkv"]).view(3 * c, c))
     bqkv = ctx.arena.span([f"{pre}to_{t}.bias" for t in "qkv"])
-    qkv = torch.empty((b * s, 3 * c), dtype=BF16, device=dev)
-    _gemm(xn, c, 0, 0, wqkv, c, 0, 0, qkv, 3 * c, 0, 0, b * s, 3 * c, c, 1, 1, bias=bqkv)
-    z = b * heads
-    sq = s * 3 * c  # batch stride of qkv
+    qkv = ops.gemm_nt(xn.view(b * s, c), wqkv, bias=bqkv)                         # [B*S, 3C]
     if FLASH_ATTENTION and _lib.call_raw("mi_attn_supported", c, heads):
         return _attention_flash(ctx, x, name, st, xn, wqkv, qkv, b, s, c, heads, scale)
-    # Materialised path (head dims the fused kernels do not cover).  Every bf16 matrix whose LAST axis is the token axis is a GEMM
-    # operand reduced over that axis: the NT GEMM loads 16-byte pieces along K, so those matrices get a row pitch `sp` = S rounded
-    # up to a multiple of 8 with zero pad columns (written by the softmax / transpose kernels themselves) and the products run
-    # over K = sp.  (3^3 = 27 or 5^3 = 125 tokens at the coarsest level of non-power-of-two patches.)
-    sp = (s + 7) // 8 * 8
-    scores = torch.empty((z, s, s), dtype=F32, device=dev)
-    _gemm((qkv, 0), 3 * c, sq, hd, (qkv, c), 3 * c, sq, hd, scores, s, heads * s * s, s * s, s, s, hd, z, heads, alpha=scale)
-    probs = ops.softmax_fwd(scores, pad8=True)                                    # [z, S, S] view, pitch sp
-    del scores
-
-    def tr_tokens(src, ld_in, si1, si2, cols):
-        """[z][S][cols] (strided) -> [z][cols][sp] with the token axis last, zero padded."""
-        out = torch.empty((z, cols, sp), dtype=BF16, device=dev)
-        a = src[0].data_ptr() + src[1] * 2 if isinstance(src, tuple) else src.data_ptr()
-        call("mi_transpose_bf16", a, ld_in, si1, si2, ptr(out), sp, heads * cols * sp, cols * sp, s, cols, z, heads)
-        return out
-
-    vt = tr_tokens((qkv, 2 * c), 3 * c, sq, hd, hd)                               # [z, hd, sp]
+    q, k, v = (_heads(qkv[:, i * c:(i + 1) * c], b, heads) for i in range(3))
     y = torch.empty_like(x)
-    _gemm(probs, sp, heads * s * sp, s * sp, vt, sp, heads * hd * sp, hd * sp, (y, 0), c, s * c, hd, s, hd, sp, z, heads,
-          res=(x, 0), ldr=c, sr1=s * c, sr2=hd)
+    sdpa_bwd = _sdpa(q, k, v, scale, out=_heads(y, b, heads), res=_heads(x, b, heads))
     ctx.count(2 * b * s * c * 3 * c)       # q, k, v projections
     ctx.count(4 * b * s * s * c)           # QK^T and PV
     if ctx.tape is not None:
@@ -629,21 +625,8 @@ def attention(ctx: Ctx, x, name, groups, eps, heads):
             dy = tape.take(y)
             if dy is None:
                 return
-            dp = torch.empty((z, s, s), dtype=F32, device=dev)
-            _gemm((dy, 0), c, s * c, hd, (qkv, 2 * c), 3 * c, sq, hd, dp, s, heads * s * s, s * s, s, s, hd, z, heads)
-            ds = ops.softmax_bwd(probs, dp, scale)                                # [z, S, S] view, pitch sp
-            del dp
             dqkv = torch.empty((b * s, 3 * c), dtype=BF16, device=dev)
-            kt = tr_tokens((qkv, c), 3 * c, sq, hd, hd)
-            _gemm(ds, sp, heads * s * sp, s * sp, kt, sp, heads * hd * sp, hd * sp, (dqkv, 0), 3 * c, sq, hd, s, hd, sp, z, heads)
-            qt = tr_tokens((qkv, 0), 3 * c, sq, hd, hd)
-            dst = tr_tokens(ds, sp, heads * s * sp, s * sp, s)                    # dS^T [z, S, sp]
-            _gemm(dst, sp, heads * s * sp, s * sp, qt, sp, heads * hd * sp, hd * sp, (dqkv, c), 3 * c, sq, hd, s, hd, sp, z, heads)
-            del dst, ds
-            pt = tr_tokens(probs, sp, heads * s * sp, s * sp, s)                  # P^T [z, S, sp]
-            dot = tr_tokens((dy, 0), c, s * c, hd, hd)
-            _gemm(pt, sp, heads * s * sp, s * sp, dot, sp, heads * hd * sp, hd * sp, (dqkv, 2 * c), 3 * c, sq, hd, s, hd, sp, z, heads)
-            del pt
+            sdpa_bwd(_heads(dy, b, heads), *(_heads(dqkv[:, i * c:(i + 1) * c], b, heads) for i in range(3)))
             _attention_param_and_input_grads(ctx, tape, x, name, st, xn, wqkv, dqkv, dy, b, s, c)
 
         tape.record(bwd)
@@ -653,28 +636,15 @@ def attention(ctx: Ctx, x, name, groups, eps, heads):
 def linear_f32(x_f32, w, b, gw, gb):
     """Tiny fp32-in / fp32-out Linear on the embedding vectors (bf16 MFMA inside).  w [out, in], b [out] and their
     gradient buffers gw, gb are fp32 arena views.  Returns (y, backward(dy) -> dx)."""
-    out_f, in_f = w.shape
     xb, wb = ops.cast_bf16(x_f32), ops.cast_bf16(w)
-    m = x_f32.shape[0]
-    y = torch.empty((m, out_f), dtype=F32, device=x_f32.device)
-    _gemm(xb, in_f, 0, 0, wb, in_f, 0, 0, y, out_f, 0, 0, m, out_f, in_f, 1, 1, bias=b)
+    y = ops.gemm_nt(xb, wb, bias=b, out_f32=True)
 
     def bwd(dy_f32, need_dx=True):
         """dy may be a column slice; accumulates into the weight/bias gradients, returns dx (fp32) or None."""
         dyb = ops.cast_bf16(dy_f32)
         ops.sum_rows_f32(dy_f32, gb, accumulate=True)
-        mp = (m + 7) // 8 * 8  # K of the weight-gradient GEMM must be a multiple of 8: the transpose kernel zero-fills [m, mp)
-        dy_t = torch.empty((out_f, mp), dtype=BF16, device=dy_f32.device)
-        x_t = torch.empty((in_f, mp), dtype=BF16, device=dy_f32.device)
-        call("mi_transpose_bf16", ptr(dyb), out_f, 0, 0, ptr(dy_t), mp, 0, 0, m, out_f, 1, 1)
-        call("mi_transpose_bf16", ptr(xb), in_f, 0, 0, ptr(x_t), mp, 0, 0, m, in_f, 1, 1)
-        _gemm(dy_t, mp, 0, 0, x_t, mp, 0, 0, gw, in_f, 0, 0, out_f, in_f, mp, 1, 1, accumulate=True)
-        if not need_dx:
-            return None
-        w_t = _transpose(wb, in_f, 0, 0, out_f, in_f, 1, 1, dy_f32.device)[0]   # [in, out]
-        dx = torch.empty((m, in_f), dtype=F32, device=dy_f32.device)
-        _gemm(dyb, out_f, 0, 0, w_t, out_f, 0, 0, dx, in_f, 0, 0, m, in_f, out_f, 1, 1)
-        return dx
+        token_wgrad(dyb, xb, out=gw)
+        return linear_dgrad(dyb, wb, out_f32=True) if need_dx else None
 
     return y, bwd
 
@@ -726,8 +696,7 @@ def linear(ctx: Ctx, x, name, bias=True, res=None, need_dx=True):
     if k % 8 or n % 8:
         raise ValueError(f"{name}: feature counts must be multiples of 8 on the HIP path (got {k} -> {n})")
     wb = ops.cast_bf16(w)
-    y = torch.empty((m, n), dtype=BF16, device=x.device)
-    _gemm(x, k, 0, 0, wb, k, 0, 0, y, n, 0, 0, m, n, k, 1, 1, bias=ctx.p(name + ".bias") if bias else None, res=res, ldr=n)
+    y = ops.gemm_nt(x, wb, bias=ctx.p(name + ".bias") if bias else None, res=res)
     ctx.count(2 * m * n * k, dgrad=need_dx)
     if ctx.tape is not None:
         tape = ctx.tape
@@ -740,10 +709,7 @@ def linear(ctx: Ctx, x, name, bias=True, res=None, need_dx=True):
             if res is not None:
                 tape.put(res, dy)
             if need_dx:
-                wt = _transpose(wb, k, 0, 0, n, k, 1, 1, x.device)[0]  # [K, N]
-                dx = torch.empty((m, k), dtype=BF16, device=x.device)
-                _gemm(dy, n, 0, 0, wt, n, 0, 0, dx, k, 0, 0, m, k, n, 1, 1)
-                tape.put(x, dx)
+                tape.put(x, linear_dgrad(dy, wb))
 
         tape.record(bwd)
     return y
@@ -771,30 +737,11 @@ def geglu(ctx: Ctx, h):
 
 def mha(ctx: Ctx, q, k, v, b, sq, skv, heads):
     """CrossAttention._attention (UNet:135-154): softmax(Q K^T / sqrt(d)) V per head; q [B*Sq, C], k / v [B*Skv, C] bf16 dense, the
-    heads are column slices (reshape_heads_to_batch_dim is free in this layout).  Materialised scores (fp32) -- the query and
-    key/value token counts differ for a context -- with every token axis that becomes a GEMM reduction axis zero-padded to a
-    multiple of 8 by the softmax / transpose kernels."""
+    heads are column slices (reshape_heads_to_batch_dim is free in this layout).  Materialised scores (_sdpa): the query and key/value
+    token counts differ for a context."""
     c = q.shape[1]
-    hd = c // heads
-    if hd % 8:
-        raise ValueError("head width must be a multiple of 8 on the HIP path")
-    scale = 1.0 / math.sqrt(hd)
-    z, dev = b * heads, q.device
-    kp, qp = (skv + 7) // 8 * 8, (sq + 7) // 8 * 8
-
-    def tr(src, rows, pad):
-        """the head slices of a [B * rows, C] token matrix -> [z][hd][pad]: token axis last, zero padded to `pad`."""
-        out = torch.empty((z, hd, pad), dtype=BF16, device=dev)
-        call("mi_transpose_bf16", ptr(src), c, rows * c, hd, ptr(out), pad, heads * hd * pad, hd * pad, rows, hd, z, heads)
-        return out
-
-    scores = torch.empty((z, sq, skv), dtype=F32, device=dev)
-    _gemm(q, c, sq * c, hd, k, c, skv * c, hd, scores, skv, heads * sq * skv, sq * skv, sq, skv, hd, z, heads, alpha=scale)
-    probs = ops.softmax_fwd(scores, pad8=True)  # [z, Sq, Skv] view, pitch kp
-    del scores
-    vt = tr(v, skv, kp)  # [z, hd, kp]
-    o = torch.empty((b * sq, c), dtype=BF16, device=dev)
-    _gemm(probs, kp, heads * sq * kp, sq * kp, vt, kp, heads * hd * kp, hd * kp, o, c, sq * c, hd, sq, hd, kp, z, heads)
+    o = torch.empty((b * sq, c), dtype=BF16, device=q.device)
+    sdpa_bwd = _sdpa(*(_heads(t, b, heads) for t in (q, k, v)), 1.0 / math.sqrt(c // heads), out=_heads(o, b, heads))
     ctx.count(4 * b * sq * skv * c)
     if ctx.tape is not None:
         tape = ctx.tape
@@ -803,27 +750,9 @@ def mha(ctx: Ctx, q, k, v, b, sq, skv, heads):
             do = tape.take(o)
             if do is None:
                 return
-            dp = torch.empty((z, sq, skv), dtype=F32, device=dev)
-            _gemm(do, c, sq * c, hd, v, c, skv * c, hd, dp, skv, heads * sq * skv, sq * skv, sq, skv, hd, z, heads)
-            ds = ops.softmax_bwd(probs, dp, scale)  # [z, Sq, Skv] view, pitch kp
-            del dp
-            kt = tr(k, skv, kp)
-            dq = torch.empty((b * sq, c), dtype=BF16, device=dev)
-            _gemm(ds, kp, heads * sq * kp, sq * kp, kt, kp, heads * hd * kp, hd * kp, dq, c, sq * c, hd, sq, hd, kp, z, heads)
-            tape.put(q, dq)
-
-            def tr_ss(src):  # [z][Sq][Skv] (pitch kp) -> [z][Skv][qp]
-                out = torch.empty((z, skv, qp), dtype=BF16, device=dev)
-                call("mi_transpose_bf16", ptr(src), kp, heads * sq * kp, sq * kp, ptr(out), qp, heads * skv * qp, skv * qp, sq, skv, z, heads)
-                return out
-
-            dst, qt = tr_ss(ds), tr(q, sq, qp)
-            dk = torch.empty((b * skv, c), dtype=BF16, device=dev)
-            _gemm(dst, qp, heads * skv * qp, skv * qp, qt, qp, heads * hd * qp, hd * qp, dk, c, skv * c, hd, skv, hd, qp, z, heads)
-            pt, dot = tr_ss(probs), tr(do, sq, qp)
-            dv = torch.empty((b * skv, c), dtype=BF16, device=dev)
-            _gemm(pt, qp, heads * skv * qp, skv * qp, dot, qp, heads * hd * qp, hd * qp, dv, c, skv * c, hd, skv, hd, qp, z, heads)
-            tape.put(k, dk), tape.put(v, dv)
+            dq, dk, dv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+            sdpa_bwd(*(_heads(t, b, heads) for t in (do, dq, dk, dv)))
+            tape.put(q, dq), tape.put(k, dk), tape.put(v, dv)
 
         tape.record(bwd)
     return o

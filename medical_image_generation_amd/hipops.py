@@ -372,36 +372,81 @@ def sum_rows_f32(x, out, accumulate=True):
 
 
 # ----------------------------------------------------------------------------- GEMM family
+# gemm_nt and transpose take torch VIEWS: last-dim stride 1, any row pitch, up to two leading batch dims (the library's z / z2, e.g.
+# [B, heads]).  Every lda / s1 / s2 handed to the library is a `.stride()` of the view and every address its `.data_ptr()`, so a head of
+# a fused [B*S, 3C] q/k/v matrix is `qkv[:, :C].view(B, S, H, hd).permute(0, 2, 1, 3)` and an output into a column block is just a view.
+def _batch(*views):
+    """Batch shape shared by the operands of one call: their leading dims, right-aligned like torch broadcasting."""
+    shapes = [tuple(v.shape[:-2]) for v in views]
+    rank = max(len(s) for s in shapes)
+    if rank > 2:
+        raise ValueError(f"at most two batch levels, got {max(shapes, key=len)}")
+    return tuple(max(col) for col in zip(*[(1,) * (rank - len(s)) + s for s in shapes]))
+
+
+def _strided(v, batch, what, vec16=False, broadcast=True):
+    """(row pitch, s1, s2) of the [.., rows, cols] view `v` in a call batched over `batch`, checked.  A batch level the view lacks, or has
+    with size 1, is broadcast with stride 0.  vec16: the kernel loads 16-byte pieces along the rows of this operand."""
+    if v is None:
+        return 0, 0, 0
+    if v.stride(-1) != 1:
+        raise ValueError(f"{what}: last-dim stride must be 1, got {v.stride(-1)}")
+    own = tuple(v.shape[:-2])
+    lead = len(batch) - len(own)
+    if lead < 0 or any(o != n and (o != 1 or not broadcast) for o, n in zip((1,) * lead + own, batch)):
+        raise ValueError(f"{what}: batch shape {own} does not {'broadcast to' if broadcast else 'equal'} {tuple(batch)}")
+    s = [0] * lead + [st if o == n else 0 for st, o, n in zip(v.stride(), own, batch[lead:])] + [0] * (2 - len(batch))
+    if vec16 and (v.stride(-2) % 8 or s[0] % 8 or s[1] % 8 or v.data_ptr() % 16):
+        raise ValueError(f"{what}: rows must start 16-byte aligned (pitch {v.stride(-2)}, batch strides {s[0]}, {s[1]} bf16 elements)")
+    return v.stride(-2), s[0], s[1]
+
+
+def _z(batch):
+    """(Z, Z2) of the library calls: all batches, and the inner level's count."""
+    return (batch[0] * batch[1], batch[1]) if len(batch) == 2 else (batch[0] if batch else 1, 1)
+
+
+def padded(v):
+    """A [.., cols] view of a zero-padded buffer (softmax_fwd(pad8=True), softmax_bwd) widened to its row pitch: the operand of a GEMM
+    that reduces over that axis (K must be a multiple of 8; the pad columns are zeros)."""
+    return v.as_strided(tuple(v.shape[:-1]) + (v.stride(-2),), v.stride())
+
+
 def gemm_nt(a, b, *, bias=None, res=None, alpha=1.0, out=None, out_f32=False, accumulate=False):
-    """out[z] = alpha * a[z] @ b[z]^T (+bias) (+res).  a: [Z?, M, K], b: [Z?, N, K] (last dim contiguous, arbitrary row pitch)."""
-    a3, b3 = (a if a.dim() == 3 else a.unsqueeze(0)), (b if b.dim() == 3 else b.unsqueeze(0))
-    z, m, k = a3.shape
-    n = b3.shape[1]
-    assert b3.shape[2] == k and a3.stride(2) == 1 and b3.stride(2) == 1
-    zb = b3.shape[0]
-    assert zb in (1, z)
+    """out = alpha * a @ b^T (+ bias) (+ res) (+ out when accumulate).  a [.., M, K], b [.., N, K] bf16 views with 16-byte aligned rows and
+    K a multiple of 8; res (bf16) / out (bf16 or fp32) [.., M, N] views of any pitch; bias fp32 [N].  a, b and res may broadcast over the
+    batch; `out` (allocated dense when None: fp32 if out_f32) spans it."""
+    (m, k), (n, kb) = a.shape[-2:], b.shape[-2:]
+    if kb != k or k % 8:
+        raise ValueError(f"gemm_nt reduces over a shared K that is a multiple of 8, got {k} and {kb}")
+    batch = _batch(a, b)
     if out is None:
-        out = torch.empty((z, m, n), dtype=F32 if out_f32 else BF16, device=a.device)
-        out_v = out
-    else:
-        out_v = out if out.dim() == 3 else out.unsqueeze(0)
-    r3 = None
-    if res is not None:
-        r3 = res if res.dim() == 3 else res.unsqueeze(0)
-        assert r3.stride(2) == 1
-    call("mi_gemm_nt_bf16", ptr(a3), a3.stride(1), a3.stride(0), 0, ptr(b3), b3.stride(1), b3.stride(0) if zb == z else 0, 0,
-         ptr(out_v), out_v.stride(1), out_v.stride(0), 0, ptr(bias), ptr(r3), r3.stride(1) if r3 is not None else 0,
-         r3.stride(0) if r3 is not None else 0, 0, m, n, k, z, 1, float(alpha), int(out_v.dtype == F32), int(accumulate))
-    return out if a.dim() == 3 or out.dim() == 2 else out[0]
+        out = torch.empty(batch + (m, n), dtype=F32 if out_f32 else BF16, device=a.device)
+    for t, what in ((out, "out"), (res, "res")):
+        if t is not None and tuple(t.shape[-2:]) != (m, n):
+            raise ValueError(f"{what}: expected [.., {m}, {n}], got {tuple(t.shape)}")
+    assert a.dtype == b.dtype == BF16 and (res is None or res.dtype == BF16) and (out.dtype == F32 or not accumulate)
+    sa, sb = _strided(a, batch, "a", vec16=True), _strided(b, batch, "b", vec16=True)
+    so, sr = _strided(out, batch, "out", broadcast=False), _strided(res, batch, "res")
+    call("mi_gemm_nt_bf16", ptr(a), *sa, ptr(b), *sb, ptr(out), *so, ptr(bias), ptr(res), *sr, m, n, k, *_z(batch), float(alpha),
+         int(out.dtype == F32), int(accumulate))
+    return out
 
 
-def transpose(x):
-    """[Z?, R, C] bf16 (last dim contiguous) -> [Z?, C, R] contiguous."""
-    x3 = x if x.dim() == 3 else x.unsqueeze(0)
-    z, r, c = x3.shape
-    out = torch.empty((z, c, r), dtype=BF16, device=x.device)
-    call("mi_transpose_bf16", ptr(x3), x3.stride(1), x3.stride(0), 0, ptr(out), r, c * r, 0, r, c, z, 1)
-    return out if x.dim() == 3 else out[0]
+def transpose(x, pad_to=None, out=None):
+    """[.., R, C] bf16 view -> dense [.., C, P] with the source's row axis last.  P = R, or with pad_to=8 R rounded up to a multiple of 8 (the
+    pitch of a GEMM reduction axis): the kernel zero-fills columns R..P.  out: write into this [.., C, P] view instead."""
+    assert pad_to in (None, 8), "the kernel zero-fills up to the next multiple of 8 only"
+    r, c = x.shape[-2:]
+    p = (r + 7) // 8 * 8 if pad_to else r
+    batch = _batch(x)
+    if out is None:
+        out = torch.empty(batch + (c, p), dtype=BF16, device=x.device)
+    if tuple(out.shape[-2:]) != (c, p) or x.dtype != BF16 or out.dtype != BF16:
+        raise ValueError(f"out: expected bf16 [.., {c}, {p}], got {out.dtype} {tuple(out.shape)}")
+    sx, so = _strided(x, batch, "x"), _strided(out, batch, "out", broadcast=False)
+    call("mi_transpose_bf16", ptr(x), *sx, ptr(out), *so, r, c, *_z(batch))
+    return out
 
 
 def softmax_fwd(scores_f32, pad8=False):

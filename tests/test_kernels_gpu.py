@@ -163,9 +163,37 @@ def test_gemm_nt(ops, m, n, k, z):
     check(out2.cpu(), wide[:, :, k:2 * k].float().cpu() @ b.transpose(1, 2), 2e-3, "gemm strided A")
 
 
+def test_gemm_nt_two_batch_levels(ops):
+    """Operands addressed the way attention heads are: [B, heads, S, hd] views of [B, S, 3 * heads * hd] matrices (batch strides and row
+    pitch from the views), fp32 output; then bf16 output into a column slice of a wider buffer with a residual view -- a wrong ldc or
+    batch stride lands in the NaN-prefilled columns around the slice."""
+    B, S, S2, H, hd = 2, 5, 7, 3, 16
+    wide, wide2 = rnd(B, S, 3 * H * hd).to(dev, torch.bfloat16), rnd(B, S2, 3 * H * hd, seed=1).to(dev, torch.bfloat16)
+    q = wide.view(B, S, 3, H, hd)[:, :, 0].permute(0, 2, 1, 3)     # [2, 3, 5, 16]
+    k = wide2.view(B, S2, 3, H, hd)[:, :, 1].permute(0, 2, 1, 3)   # [2, 3, 7, 16]
+    ref = q.float().cpu() @ k.float().cpu().transpose(-1, -2)
+    out = ops.gemm_nt(q, k, out_f32=True)
+    assert out.shape == (B, H, S, S2) and out.dtype == torch.float32
+    check(out.cpu(), ref, 2e-3, "gemm head views")
+    buf = torch.full((B, H, S, 16), float("nan"), dtype=torch.bfloat16, device=dev)
+    res = rnd(B, H, S, 20, seed=2).to(dev, torch.bfloat16)[..., 5:5 + S2]
+    got = ops.gemm_nt(q, k, out=buf[..., 3:3 + S2], res=res)
+    assert got.data_ptr() == buf[..., 3:3 + S2].data_ptr()
+    check(buf[..., 3:3 + S2].float().cpu(), ref + res.float().cpu(), 1e-2, "gemm head views into a column slice")
+    assert bool(torch.isnan(buf[..., :3]).all()) and bool(torch.isnan(buf[..., 3 + S2:]).all())
+
+
 def test_transpose_softmax(ops):
     x = rnd(3, 70, 130).to(dev, torch.bfloat16)
     assert torch.equal(ops.transpose(x), x.transpose(1, 2).contiguous())
+    # a [B, heads, S, hd] head view of a wider matrix -> [B, heads, hd, S rounded up to 8], pad columns zeroed by the kernel
+    hv = rnd(2, 5, 3 * 3 * 16, seed=11).to(dev, torch.bfloat16).view(2, 5, 3, 3, 16)[:, :, 2].permute(0, 2, 1, 3)
+    out = torch.full((2, 3, 16, 8), float("nan"), dtype=torch.bfloat16, device=dev)
+    t = ops.transpose(hv, pad_to=8, out=out)
+    assert t.data_ptr() == out.data_ptr() and t.shape == (2, 3, 16, 8)
+    assert torch.equal(t[..., :5], hv.transpose(-1, -2)) and bool((t[..., 5:] == 0).all())
+    t2 = ops.transpose(hv, pad_to=8)
+    assert t2.shape == (2, 3, 16, 8) and t2.is_contiguous() and torch.equal(t2[..., :5], t[..., :5]) and bool((t2[..., 5:] == 0).all())
     s = rnd(2, 50, 777, scale=3.0)
     p = ops.softmax_fwd(s.to(dev))
     check(p.float().cpu(), torch.softmax(s, -1), 1e-2, "softmax")
