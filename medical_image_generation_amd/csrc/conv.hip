@@ -813,9 +813,17 @@ typedef __attribute__((address_space(3))) void lds_void_t;
 __device__ unsigned long long g_wg2_clk[8];
 #define WG2_T0() const unsigned long long tt0__ = __builtin_amdgcn_s_memtime()
 #define WG2_T1(acc) (acc) += __builtin_amdgcn_s_memtime() - tt0__
+void wg2_diag_report() {  // host half, after a launch
+  unsigned long long h[8];
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg2_clk), sizeof(h));
+  fprintf(stderr, "[wgrad2] workgroup 0: compute wave 0: %llu cycles over %llu tiles (%llu taps), %llu inside the barrier | loader wave 8: %llu cycles = issue %llu + vmcnt wait %llu + barrier %llu\n",
+          h[4], h[6], h[7], h[5], h[0], h[1], h[2], h[3]);
+}
 #else
 #define WG2_T0() do {} while (0)
 #define WG2_T1(acc) do {} while (0)
+inline void wg2_diag_report() {}
 #endif
 
 template <int MAXP>
@@ -1198,8 +1206,43 @@ constexpr int WR_LDS = WR_XRING + 2 * WR_YB + 64;
 __device__ unsigned long long g_wg3_clk[16];
 __device__ unsigned long long g_wg3_span[6][1024];  // entry / exit / end of compute wave 0's tile loop / its prologue barrier, per workgroup
 #define WG3_STAMP(i) do { if (blockIdx.x == 0 && lane == 0) g_wg3_clk[i] = wall_clock64(); } while (0)
+void wg3_diag_arm() {  // host half, before a launch: zero the stamps
+  unsigned long long h0[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0};
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg3_clk), h0, sizeof(h0));
+  static unsigned long long z[6][1024];
+  (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg3_span), z, sizeof(z));
+}
+void wg3_diag_report(int Cin, int Cout, int ntiles, int nsplit, unsigned nwg) {  // ... after it: read back, print
+  unsigned long long h[16];
+  (void)hipDeviceSynchronize();
+  (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg3_clk), sizeof(h));
+  auto us = [&](int a, int b) { return (double)((long long)h[b] - (long long)h[a]) / 100.0; };
+  fprintf(stderr, "[wgrad3 %d->%d ntiles %d nsplit %d] all workgroups: first entry -> last exit %.2f us | workgroup 0 (from the first entry): entry %.2f, "
+          "compute wave 0: setup %.2f, prologue barrier %.2f, tiles %.2f, final barrier %.2f, stores issued %.2f, stores landed %.2f | loader wave: "
+          "descriptors %.2f, prologue issue %.2f, landed %.2f us\n", Cin, Cout, ntiles, nsplit, us(14, 15), us(14, 0), us(0, 1), us(1, 2), us(2, 3), us(3, 4),
+          us(4, 5), us(5, 6), us(8, 9), us(9, 10), us(10, 11));
+  static unsigned long long sp[6][1024];
+  (void)hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_wg3_span), sizeof(sp));
+  std::vector<double> ent, dur, ext, lp, pro, bar, iss;
+  for (unsigned b = 0; b < nwg && b < 1024; ++b)
+    if (sp[1][b]) { bar.push_back((double)(sp[4][b] - h[14]) / 100.0); iss.push_back((double)(sp[5][b] - h[14]) / 100.0); lp.push_back((double)(sp[2][b] - h[14]) / 100.0); pro.push_back((double)(sp[3][b] - h[14]) / 100.0); ent.push_back((double)(sp[0][b] - h[14]) / 100.0); ext.push_back((double)(sp[1][b] - h[14]) / 100.0); dur.push_back((double)(sp[1][b] - sp[0][b]) / 100.0); }
+  std::sort(ent.begin(), ent.end()); std::sort(dur.begin(), dur.end()); std::sort(ext.begin(), ext.end());
+  std::sort(lp.begin(), lp.end()); std::sort(pro.begin(), pro.end()); std::sort(bar.begin(), bar.end()); std::sort(iss.begin(), iss.end());
+  if (!ent.empty()) fprintf(stderr, "    final barrier passed min %.2f median %.2f max %.2f | wave 0 stores issued min %.2f median %.2f max %.2f us\n", bar.front(), bar[bar.size() / 2],
+                            bar.back(), iss.front(), iss[iss.size() / 2], iss.back());
+  if (!ent.empty()) fprintf(stderr, "    prologue done min %.2f median %.2f max %.2f | tile loop done min %.2f median %.2f max %.2f us\n", pro.front(), pro[pro.size() / 2], pro.back(),
+                            lp.front(), lp[lp.size() / 2], lp.back());
+  if (!ent.empty()) {
+    auto qt = [](const std::vector<double>& v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
+    fprintf(stderr, "    %zu workgroups: entry 10%% %.2f median %.2f 90%% %.2f max %.2f | exit min %.2f median %.2f max %.2f | lifetime min %.2f median %.2f 90%% %.2f max %.2f us\n",
+            ent.size(), qt(ent, 0.1), qt(ent, 0.5), qt(ent, 0.9), ent.back(), ext.front(), qt(ext, 0.5), ext.back(), dur.front(), qt(dur, 0.5), qt(dur, 0.9), dur.back());
+  }
+}
 #else
 #define WG3_STAMP(i) do { } while (0)
+inline void wg3_diag_arm() {}
+inline void wg3_diag_report(int, int, int, int, unsigned) {}
 #endif
 
 __global__ void __launch_bounds__(768, 3) k_conv_wgrad3(WgradArgs w) {
@@ -2140,6 +2183,50 @@ int env_int(const char* name, int dflt) {
   return v ? atoi(v) : dflt;
 }
 
+// Bytes of a bf16 tensor [N][d][h][w] at channel pitch cs (> 0) when they fit the 32-bit range of a buffer descriptor, else 0.  What 0
+// means is the caller's: "unbounded" for some fields, MI_ERR_UNSUPPORTED for others.
+unsigned span32(int N, int d, int h, int w, int cs) {
+  const int64_t b = (int64_t)N * d * h * w * cs * 2;
+  return b < (1ll << 32) ? (unsigned)b : 0u;
+}
+// Raise a kernel's dynamic-LDS limit to 160 KiB once (not a stream op).  `done` is the call site's static flag, one per KERNEL:
+// k_conv_wgrad2<true> / <false>, k_conv_wgrad3 and k_wgrad_up share one function-pointer type.
+int raise_lds_limit(const void* kern, bool& done) {
+  if (done) return 0;
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  if (e != hipSuccess) return (int)e;
+  done = true;
+  return 0;
+}
+// ConvArgs fields that come from a (Tables, Geom) pair; a.N, a.Di.. and a.x_cs (the tensor the loader reads) are set.  ntiles: the tile count.
+int conv_args_tables(ConvArgs& a, const Tables& T, const Geom& g, int& ntiles) {
+  a.wpk = T.d_wpk; a.hdr = T.d_hdr; a.taps = T.d_taps; a.nchunks = T.nchunks;
+  a.wpk_bytes = (unsigned)T.nfrags * 1024u; a.g = g;
+  ntiles = a.N * g.tilesD * g.tilesH * g.tilesW;
+  return (a.x_bytes = span32(a.N, a.Di, a.Hi, a.Wi, a.x_cs)) ? 0 : MI_ERR_UNSUPPORTED;
+}
+
+// Weight-gradient kernels (k_conv_wgrad[2,3], k_wgrad_up): one workgroup per (pair, split); from 8 splits on, XCD-aware placement
+unsigned wgrad_grid(int npairs, int nsplit) { return nsplit >= 8 ? npairs * ((nsplit + 7) / 8) * 8 : npairs * nsplit; }
+bool wgrad_contig(int ntiles, int nsplit) {
+  static const int contig_env = env_int("MI_WGRAD_CONTIG", 1);
+  return contig_env && (ntiles % 8 == 0) && (nsplit % 8 == 0) && nsplit <= ntiles;
+}
+// Number of splits of the tile range.  One workgroup per CU (112 KB of LDS each), and workgroup i of a launch goes to XCD i % 8: an XCD
+// that is dealt more than its 32 CUs' worth runs a second round.  Rounding 256 / npairs UP (what this did) deals 33 workgroups to five
+// XCDs for 3 pairs (96 -> 32), and the launch takes twice as long: 554 us where 32 -> 32, a third of the work, takes 123.  Cost of a
+// split, in hundredths of a tile time = 100 x rounds x (tiles per workgroup + fixed_tiles) + slab_term per split; ties go to the coarser split.
+int pick_nsplit(int ntiles, int npairs, int fixed_tiles, int64_t slab_term) {
+  int nsplit = 1;
+  int64_t best = -1;
+  for (int ns = 1; ns <= 256 && ns <= ntiles; ++ns) {
+    const int per_xcd = ns >= 8 ? npairs * ((ns + 7) / 8) : (npairs * ns + 7) / 8;  // (wgrad_grid)
+    const int64_t rounds = (per_xcd + 31) / 32, cost = 100 * rounds * ((ntiles + ns - 1) / ns + fixed_tiles) + slab_term * ns;
+    if (best < 0 || cost < best) { best = cost; nsplit = ns; }
+  }
+  return nsplit;
+}
+
 template <int NCB, int VB, int RING, int WPS, int MODE>
 int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   if (MODE != 0 && (a.g.row != F27_ROW || a.g.slice != F27_SLICE || a.g.TD != 4 || a.g.TH != 8 || a.g.TW != 8)) return MI_ERR_BAD_ARG;
@@ -2158,12 +2245,8 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
 #define MI_LAUNCH_NP(NPV)                                                                                  \
   do {                                                                                                     \
     auto kern = k_conv_igemm<NCB, VB, NPV, RING, WPS, MODE>;                                               \
-    static int lds_ok = 0; /* raise the dynamic-LDS limit once per instantiation (not a stream op) */      \
-    if ((int)lds > lds_ok) {                                                                               \
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e != hipSuccess) return (int)e;                                                                  \
-      lds_ok = 160 * 1024;                                                                                 \
-    }                                                                                                      \
+    static bool raised = false; /* one flag per instantiation */                                           \
+    if (int e = raise_lds_limit((const void*)kern, raised)) return e;                                      \
     hipLaunchKernelGGL(kern, grid, blk, lds, st, a);                                                       \
   } while (0)
   if constexpr (MODE != 0) {  // fixed 4x8x8 (+halo) geometry: 2400 pieces -> 10 per thread
@@ -2262,8 +2345,8 @@ int phase_side_pack(PhaseSide& ps, const float* w, int Co_t, int Ci_t, hipStream
 int phase_side_run(const PhaseSide& ps, const void* x, int x_cs, int id, int ih, int iw, void* y, int y_cs, int od, int oh, int ow, int N,
                    const float* addvec, int addvec_stride, hipStream_t st) {
   if (!ps.mode || (x_cs & 7) || (y_cs & 7)) return MI_ERR_UNSUPPORTED;
-  const int64_t xb = (int64_t)N * id * ih * iw * x_cs * 2, yb = (int64_t)N * od * oh * ow * y_cs * 2;
-  if (xb >= (1ll << 32) || yb >= (1ll << 32) || (int64_t)ps.nfrags * 1024 >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
+  const unsigned xb = span32(N, id, ih, iw, x_cs), yb = span32(N, od, oh, ow, y_cs);
+  if (!xb || !yb || (int64_t)ps.nfrags * 1024 >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
   ConvArgs a;
   memset(&a, 0, sizeof(a));
   a.x = (const bf16*)x; a.x_cs = x_cs; a.N = N; a.Di = id; a.Hi = ih; a.Wi = iw; a.Cin = ps.Ki;
@@ -2271,7 +2354,7 @@ int phase_side_run(const PhaseSide& ps, const void* x, int x_cs, int id, int ih,
   a.ogpq = ps.ny; a.outc_q = ps.Ko;
   a.wpk = ps.d_w; a.wpk_bytes = (unsigned)ps.nfrags * 1024u; a.nchunks = ps.nchunks;
   a.addvec = addvec; a.addvec_stride = addvec_stride;
-  a.x_bytes = (unsigned)xb; a.y_bytes = (unsigned)yb;
+  a.x_bytes = xb; a.y_bytes = yb;
   a.perm16 = 1;
   a.g = ps.g;
   const int ntiles = N * a.g.tilesD * a.g.tilesH * a.g.tilesW;
@@ -2290,15 +2373,7 @@ int upconv_wgrad_tables(mi_conv_plan* P) {
   const int npairs = ny * nch * 2;  // (cout block, cin chunk, d-parity half of the phases)
   P->wg_split_stride = (int64_t)ny * nch * 64 * 1024;
   const int ntiles = P->N * g.tilesD * g.tilesH * g.tilesW;
-  int nsplit = 1;
-  {  // (the cost model of mi_conv_plan_create: rounds per XCD x (tiles per workgroup + fixed costs); a tile here is 8 phase steps)
-    int64_t best = -1;
-    for (int ns = 1; ns <= 256 && ns <= ntiles; ++ns) {
-      const int per_xcd = ns >= 8 ? npairs * ((ns + 7) / 8) : (npairs * ns + 7) / 8;
-      const int64_t rounds = (per_xcd + 31) / 32, cost = rounds * ((ntiles + ns - 1) / ns + 2);
-      if (best < 0 || cost < best) { best = cost; nsplit = ns; }
-    }
-  }
+  int nsplit = pick_nsplit(ntiles, npairs, 2, 0);  // (a tile here is 8 phase steps)
   static const int ns_env = env_int("MI_WGU_NSPLIT", 0);
   if (ns_env > 0 && ns_env <= ntiles) nsplit = ns_env;
   while (nsplit > 1 && (int64_t)nsplit * P->wg_split_stride * 4 > (256ll << 20)) nsplit /= 2;
@@ -2315,30 +2390,22 @@ int upconv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int d
   ConvArgs& a = w.c;
   a.x = (const bf16*)x; a.x_cs = x_cs; a.N = P->N; a.Di = P->Di; a.Hi = P->Hi; a.Wi = P->Wi; a.Cin = P->Cin;
   a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;  // dY: the fine grid
-  a.nchunks = P->up_nch;
-  a.g = P->g_wg;
-  const int64_t xb = (int64_t)P->N * P->Di * P->Hi * P->Wi * x_cs * 2, dyb = (int64_t)P->N * P->Do * P->Ho * P->Wo * dy_cs * 2;
-  if (xb >= (1ll << 32) || dyb >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
-  a.x_bytes = (unsigned)xb;
-  w.dy = (const bf16*)dy; w.dy_cs = dy_cs; w.dy_bytes = (unsigned)dyb;
+  a.nchunks = P->up_nch; a.g = P->g_wg;
+  a.x_bytes = span32(P->N, P->Di, P->Hi, P->Wi, x_cs);
+  w.dy = (const bf16*)dy; w.dy_cs = dy_cs; w.dy_bytes = span32(P->N, P->Do, P->Ho, P->Wo, dy_cs);
+  if (!a.x_bytes || !w.dy_bytes) return MI_ERR_UNSUPPORTED;
   w.sx = 1; w.sy = 2; w.cs_chunks = 1;
   w.part = P->d_part; w.split_stride = P->wg_split_stride;
   w.ntiles = P->N * a.g.tilesD * a.g.tilesH * a.g.tilesW;
   w.nsplit = P->wg_nsplit;
-  static const int contig_env = env_int("MI_WGRAD_CONTIG", 1);
-  w.contig = contig_env && (w.ntiles % 8 == 0) && (w.nsplit % 8 == 0) && w.nsplit <= w.ntiles;
+  w.contig = wgrad_contig(w.ntiles, w.nsplit);
   w.colsum = dy_colsum; w.colsum_stride = dy_colsum_stride;
   w.cs_part = dy_colsum ? P->d_cspart : nullptr;
   w.npairs = P->wg.ny * P->up_nch * 2;
   const size_t lds = 2 * WGU_XSLOT + WGU_NBY * WGU_YSLOT + 64;
-  static bool attr = false;
-  if (!attr) {
-    hipError_t e = hipFuncSetAttribute((const void*)k_wgrad_up, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr = true;
-  }
-  dim3 grid(w.nsplit >= 8 ? w.npairs * ((w.nsplit + 7) / 8) * 8 : w.npairs * w.nsplit);
-  hipLaunchKernelGGL(k_wgrad_up, grid, dim3(768), lds, st, w);
+  static bool raised = false;
+  if (int e = raise_lds_limit((const void*)k_wgrad_up, raised)) return e;
+  hipLaunchKernelGGL(k_wgrad_up, dim3(wgrad_grid(w.npairs, w.nsplit)), dim3(768), lds, st, w);
   CsReduce cs{w.cs_part, P->wg_nsplit * 8, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0};
   cs.nbx = (cs.Cout + 31) / 32;
   const int extra = cs.part ? cs.nbx * cs.N : 0, nmain = P->wg.ny * P->up_nch * 32;
@@ -2348,92 +2415,62 @@ int upconv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int d
   return 0;
 }
 
-}  // namespace
-
-extern "C" {
-
-int mi_conv_plan_create(mi_conv_plan** out, int N, int Di, int Hi, int Wi, int Cin, int Cout, const int* k, const int* s, const int* p) {
-  if (!out || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return MI_ERR_BAD_ARG;
-  mi_conv_plan* P = new mi_conv_plan();
-  P->N = N; P->Di = Di; P->Hi = Hi; P->Wi = Wi; P->Cin = Cin; P->Cout = Cout;
-  std::vector<AxisCombo> cf[3], cdg[3];
-  int dims[3] = {Di, Hi, Wi}, od[3], halo_f[3] = {0, 0, 0}, halo_d[3] = {0, 0, 0};
-  for (int a = 0; a < 3; ++a) {
-    P->k[a] = k[a]; P->s[a] = s[a]; P->p[a] = p[a];
-    if (!axis_combos_fwd(k[a], s[a], p[a], cf[a], P->f[a]) || !axis_combos_dgrad(k[a], s[a], p[a], cdg[a])) {
-      delete P;
-      return MI_ERR_UNSUPPORTED;
-    }
-    od[a] = (dims[a] + 2 * p[a] - k[a]) / s[a] + 1;
-    for (auto& c : cf[a]) if (c.delta != 0) halo_f[a] = 1;
-    for (auto& c : cdg[a]) if (c.delta != 0) halo_d[a] = 1;
-  }
-  P->Do = od[0]; P->Ho = od[1]; P->Wo = od[2];
-  P->Q = P->f[0] * P->f[1] * P->f[2];
-  P->strided = P->Q > 1;
-  P->Dp = (Di + P->f[0] - 1) / P->f[0]; P->Hp = (Hi + P->f[1] - 1) / P->f[1]; P->Wp = (Wi + P->f[2] - 1) / P->f[2];
-  P->KT = k[0] * k[1] * k[2];
+// ---- plan set-up: each step returns 0 or an error; the caller destroys the half-built plan (every pointer starts null)
+// Route flags, channels per workgroup (ncb) and geometries; the buffers of the single-channel and the 1x1 GEMM routes
+int conv_plan_routes(mi_conv_plan* P, const int halo_f[3], const int halo_d[3]) {
+  const int N = P->N, Cin = P->Cin, Cout = P->Cout, od[3] = {P->Do, P->Ho, P->Wo};
   P->full27 = true;
-  for (int a = 0; a < 3; ++a) P->full27 = P->full27 && k[a] == 3 && s[a] == 1 && p[a] == 1;
+  for (int a = 0; a < 3; ++a) P->full27 = P->full27 && P->k[a] == 3 && P->s[a] == 1 && P->p[a] == 1;
   // parity classes start at q*Cin: 16-byte loads need Cin % 8 == 0.  A class that is not a multiple of 32 channels is
   // read together with the head of the next class; those extra k-rows meet zero weights (pack masks ci >= Cin).
-  if (P->strided && (Cin % 8) != 0) { delete P; return MI_ERR_UNSUPPORTED; }
+  if (P->strided && (Cin % 8) != 0) return MI_ERR_UNSUPPORTED;
   // 64 output channels per workgroup run ~10 % more MFMA per second than 32 (fewer LDS bytes per MFMA), but a channel count that is an
   // odd multiple of 32 pads its last workgroup row with 32 dead channels: for 96 that is a third more MFMAs than needed (the data
   // gradient of the 96 -> 32 conv of the finest up-block: 434 us as 64 + 32(+32 dead), ~345 as 3 x 32)
   P->ncb_fwd = Cout > 32 && Cout != 96 ? 2 : 1;
-  {  // only the 32-channel variant carries the GroupNorm sums in its epilogue (above): up to this many output channels the forward runs
-     // as rows of 32 so that the consumer's statistics pass disappears (A/B knob; 32 = the plain rule)
-    static const int ncb1_max = env_int("MI_NCB1_FWD_MAXC", 32);
-    if (Cout <= ncb1_max && (Cout % 32) == 0) P->ncb_fwd = 1;
-  }
+  // only the 32-channel variant carries the GroupNorm sums in its epilogue (above): up to this many output channels the forward runs
+  // as rows of 32 so that the consumer's statistics pass disappears (A/B knob; 32 = the plain rule)
+  static const int ncb1_max = env_int("MI_NCB1_FWD_MAXC", 32);
+  if (Cout <= ncb1_max && (Cout % 32) == 0) P->ncb_fwd = 1;
   P->ncb_dg = Cin > 32 && Cin != 96 ? 2 : 1;
-  {  // few tiles (16^3 levels): 64 output channels per workgroup would leave most CUs without a workgroup -> 32 per workgroup
-    const int64_t tiles = (int64_t)N * ((od[0] + 3) / 4) * ((od[1] + 7) / 8) * ((od[2] + 7) / 8);
-    if (od[0] > 1 && tiles * ((Cout + 63) / 64) <= 128) P->ncb_fwd = 1;
-    if (od[0] > 1 && tiles * ((Cin + 63) / 64) <= 128) P->ncb_dg = 1;
-  }
+  // few tiles (16^3 levels): 64 output channels per workgroup would leave most CUs without a workgroup -> 32 per workgroup
+  const int64_t tiles = (int64_t)N * ((od[0] + 3) / 4) * ((od[1] + 7) / 8) * ((od[2] + 7) / 8);
+  if (od[0] > 1 && tiles * ((Cout + 63) / 64) <= 128) P->ncb_fwd = 1;
+  if (od[0] > 1 && tiles * ((Cin + 63) / 64) <= 128) P->ncb_dg = 1;
   // forward: loader reads x (or its depth image: dims Dp.., Q*Cin channels); outputs on the (Do,Ho,Wo) grid
   P->g_fwd = make_geom(2, P->Do, P->Ho, P->Wo, halo_f, N);
+  // dgrad: loader reads dy (Do,Ho,Wo,Cout); outputs the depth image of dx on the (Dp,Hp,Wp) grid with Q*Cin channels
+  P->g_dg = make_geom(2, P->Dp, P->Hp, P->Wp, halo_d, N);
+  // wgrad: forward geometry, 32-cout groups
+  P->g_wg = make_geom(2, P->Do, P->Ho, P->Wo, halo_f, N, 64);
+  static const int use_c1 = env_int("MI_CONV_C1", 1);
+  auto c_ok = [](int c) { return c >= 8 && c <= 64 && (c & 7) == 0; };
+  P->c1_in = use_c1 && P->full27 && Cin == 1 && c_ok(Cout);
+  P->c1_out = use_c1 && P->full27 && Cout == 1 && c_ok(Cin);
   static const int use27 = env_int("MI_CONV27", 1);  // 0: keep every conv on the table-driven kernel (A/B runs)
-  {
-    static const int use_c1 = env_int("MI_CONV_C1", 1);
-    auto c_ok = [](int c) { return c >= 8 && c <= 64 && (c & 7) == 0; };
-    P->c1_in = use_c1 && P->full27 && Cin == 1 && c_ok(Cout);
-    P->c1_out = use_c1 && P->full27 && Cout == 1 && c_ok(Cin);
-    if (P->c1_in || P->c1_out) {
-      const int C = P->c1_in ? Cout : Cin;
-      if (hipMalloc((void**)&P->d_c1w, (size_t)27 * C * 4) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
-      if (hipMalloc((void**)&P->d_c1part, (size_t)mi_c1_wgrad_scratch_floats(C) * 4) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
-    }
-  }
   const bool geo27 = P->full27 && P->g_fwd.TD == 4 && P->g_fwd.TH == 8 && P->g_fwd.TW == 8;
   P->v27_fwd = use27 && geo27 && (Cin % 8) == 0 && (Cout % 8) == 0;  // whole channel octets on both sides (else: table-driven kernel)
   P->v27_dg = use27 && geo27 && (Cout % 8) == 0 && (Cin % 8) == 0;
-  {
-    static const int use11 = env_int("MI_CONV1X1", 1);
-    const bool k1 = P->KT == 1 && !P->strided;
-    auto chunks_ok = [](int c) { int n = (c + 31) / 32; return n == 1 || n == 2 || n == 3 || n == 4 || n == 6; };
-    P->v11_fwd = use11 && k1 && (Cin % 8) == 0 && chunks_ok(Cin) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
-    P->v11_dg = use11 && k1 && (Cout % 8) == 0 && chunks_ok(Cout) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
-    static const int use_g11 = env_int("MI_CONV1X1_GEMM", 1);  // 0: the table-driven kernel for those layers (A/B runs)
-    P->g11 = use_g11 && k1 && (!P->v11_fwd || !P->v11_dg) && (Cin % 8) == 0 && (Cout % 8) == 0;
-    if (P->g11 && (hipMalloc((void**)&P->d_w11, (size_t)Cin * Cout * 2) != hipSuccess || hipMalloc((void**)&P->d_w11t, (size_t)Cin * Cout * 2) != hipSuccess)) {
-      mi_conv_plan_destroy(P);
-      return (int)hipErrorOutOfMemory;
-    }
+  static const int use11 = env_int("MI_CONV1X1", 1);
+  const bool k1 = P->KT == 1 && !P->strided;
+  auto chunks_ok = [](int c) { int n = (c + 31) / 32; return n == 1 || n == 2 || n == 3 || n == 4 || n == 6; };
+  P->v11_fwd = use11 && k1 && (Cin % 8) == 0 && chunks_ok(Cin) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
+  P->v11_dg = use11 && k1 && (Cout % 8) == 0 && chunks_ok(Cout) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
+  static const int use_g11 = env_int("MI_CONV1X1_GEMM", 1);  // 0: the table-driven kernel for those layers (A/B runs)
+  P->g11 = use_g11 && k1 && (!P->v11_fwd || !P->v11_dg) && (Cin % 8) == 0 && (Cout % 8) == 0;
+  if (P->c1_in || P->c1_out) {
+    const int C = P->c1_in ? Cout : Cin;
+    if (hipMalloc((void**)&P->d_c1w, (size_t)27 * C * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
+    if (hipMalloc((void**)&P->d_c1part, (size_t)mi_c1_wgrad_scratch_floats(C) * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
   }
-  build_tables(P->fwd, P->g_fwd, P->ncb_fwd, cf, P->f, P->k, true, Cin, Cout, false, P->v27_fwd || P->v11_fwd);
-  // dgrad: loader reads dy (Do,Ho,Wo,Cout); outputs the depth image of dx on the (Dp,Hp,Wp) grid with Q*Cin channels
-  P->g_dg = make_geom(2, P->Dp, P->Hp, P->Wp, halo_d, N);
-  build_tables(P->dg, P->g_dg, P->ncb_dg, cdg, P->f, P->k, false, Cout, Cin, true, P->v27_dg || P->v11_dg);
-  // wgrad: forward geometry, 32-cout groups
-  P->g_wg = make_geom(2, P->Do, P->Ho, P->Wo, halo_f, N, 64);
-  build_tables(P->wg, P->g_wg, 1, cf, P->f, P->k, true, Cin, Cout, false);
-  int e;
-  if ((e = upload_tables(P->fwd, true)) || (e = upload_tables(P->dg, true)) || (e = upload_tables(P->wg, false))) { mi_conv_plan_destroy(P); return e; }
-  // wgrad partial slabs: per pair, ntaps * 1024 floats
-  int npairs = P->wg.ny * P->wg.nchunks;
+  if (P->g11 && (hipMalloc((void**)&P->d_w11, (size_t)Cin * Cout * 2) != hipSuccess || hipMalloc((void**)&P->d_w11t, (size_t)Cin * Cout * 2) != hipSuccess))
+    return (int)hipErrorOutOfMemory;
+  return 0;
+}
+
+// Weight-gradient pairs (cout block, cin chunk), their partial slabs (per pair, ntaps * 1024 floats) and the number of splits
+int conv_plan_wgrad_slabs(mi_conv_plan* P) {
+  const int npairs = P->wg.ny * P->wg.nchunks;
   int64_t off = 0;
   P->wg_pair_off.resize(npairs);
   for (int pr = 0; pr < npairs; ++pr) {
@@ -2448,25 +2485,12 @@ int mi_conv_plan_create(mi_conv_plan** out, int N, int Di, int Hi, int Wi, int C
   }
   P->wg_split_stride = off;
   P->wg_nitems = (int)(off / 1024);
-  int ntiles = N * P->g_wg.tilesD * P->g_wg.tilesH * P->g_wg.tilesW;
-  // One workgroup per CU (112 KB of LDS each), and workgroup i of a launch goes to XCD i % 8: an XCD that is dealt more than its 32
-  // CUs' worth runs a second round.  Rounding 256 / npairs UP (what this did) deals 33 workgroups to five XCDs for 3 pairs (96 -> 32),
-  // and the launch takes twice as long: 554 us where 32 -> 32, a third of the work, takes 123.  Cost of a split = rounds x (tiles per
-  // workgroup + 6: prologue, accumulator flush and the slab it adds to the reduce, in tile times -- three rounds of 32 tiles measured
-  // 383 us against ~305 for one round of 103); ties go to the coarser split.
-  int nsplit = 1;
-  {
-    int64_t best = -1;
-    for (int ns = 1; ns <= 256 && ns <= ntiles; ++ns) {
-      const int per_xcd = ns >= 8 ? npairs * ((ns + 7) / 8) : (npairs * ns + 7) / 8;  // (k_conv_wgrad[2]: XCD-aware placement from 8 splits on)
-      // (+ optionally the slab round trip: every split writes its slab and the reduce kernel reads it back; MI_WGRAD_SLAB_COST =
-      // hundredths of a tile time per MB and split -- 2 x 1 MB / 3 TB/s = 0.67 us = ~22; measured: no setting moves the step, default 0)
-      static const int slab_cost = env_int("MI_WGRAD_SLAB_COST", 0);
-      const int64_t rounds = (per_xcd + 31) / 32;
-      const int64_t cost = 100 * rounds * ((ntiles + ns - 1) / ns + 6) + (int64_t)slab_cost * ns * (off * 4 / (1 << 20));
-      if (best < 0 || cost < best) { best = cost; nsplit = ns; }
-    }
-  }
+  const int ntiles = P->N * P->g_wg.tilesD * P->g_wg.tilesH * P->g_wg.tilesW;
+  // + 6 tile times per workgroup: prologue, accumulator flush and the slab it adds to the reduce (three rounds of 32 tiles measured 383 us
+  // against ~305 for one round of 103).  Optionally + the slab round trip: every split writes its slab and the reduce kernel reads it back;
+  // MI_WGRAD_SLAB_COST = hundredths of a tile time per MB and split -- 2 x 1 MB / 3 TB/s = 0.67 us = ~22; measured: no setting moves the step
+  static const int slab_cost = env_int("MI_WGRAD_SLAB_COST", 0);
+  int nsplit = pick_nsplit(ntiles, npairs, 6, (int64_t)slab_cost * (off * 4 / (1 << 20)));
   static const int old_split = env_int("MI_WGRAD_SPLIT_OLD", 0);  // A/B knob: the round-1 choice
   if (old_split) nsplit = (256 + npairs - 1) / npairs;
   static const int force_split = env_int("MI_WGRAD_NSPLIT", 0);  // probe knob: this many splits for every layer of at most 64 tiles
@@ -2475,34 +2499,100 @@ int mi_conv_plan_create(mi_conv_plan** out, int N, int Di, int Hi, int Wi, int C
   while (nsplit > 1 && (int64_t)nsplit * off * 4 > (256ll << 20)) nsplit /= 2;  // cap the slab at 256 MiB
   if (nsplit < 1) nsplit = 1;
   P->wg_nsplit = nsplit;
-  if ((e = upload(P->wg_pair_off, &P->d_pair_off)) || (e = upload(P->wg_uitems, &P->d_uitems))) { mi_conv_plan_destroy(P); return e; }
-  if (hipMalloc((void**)&P->d_part, (size_t)nsplit * off * 4) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
-  if (hipMalloc((void**)&P->d_cspart, (size_t)nsplit * N * Cout * 4) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
-  {  // k3 s2 p1 on all three axes: forward and data gradient on the phase kernels (no space-to-depth copies of x / dx)
-    static const int use_ph = env_int("MI_CONVPH", 1);
-    bool s2all = Di > 1;
-    for (int a = 0; a < 3; ++a) s2all = s2all && k[a] == 3 && s[a] == 2 && p[a] == 1;
-    if (use_ph && s2all && (Cin % 8) == 0 && (Cout % 8) == 0) {
-      int e1 = phase_side_create(P->ph_fwd, S2_FWD, 2, 0, Cout, Cin, P->Do, P->Ho, P->Wo, N);
-      int e2 = e1 ? e1 : phase_side_create(P->ph_dg, S2_DG, 1, 1, Cin, Cout, P->Do, P->Ho, P->Wo, N);
-      if (e1 || e2) { phase_side_free(P->ph_fwd); phase_side_free(P->ph_dg); if ((e1 ? e1 : e2) != MI_ERR_UNSUPPORTED) { mi_conv_plan_destroy(P); return e1 ? e1 : e2; } }
-      if (P->ph_fwd.mode && (Cin % 32) == 0) {  // weight gradient: the class images are gathered from x in place (k_conv_wgrad2, sx = 2)
-        std::vector<int> h2 = P->wg.hdr;
-        const int cpq = Cin / 32;  // chunks per class
-        for (int pr = 0; pr < P->wg.ny * P->wg.nchunks; ++pr) {
-          const int ch = pr % P->wg.nchunks, q = ch / cpq;
-          h2[(size_t)pr * 4 + 2] = (ch % cpq) * 32;
-          h2[(size_t)pr * 4 + 3] = q;  // (qd, qh, qw) = bits 2, 1, 0: all three factors are 2
-        }
-        if ((e = upload(h2, &P->d_hdr2))) { mi_conv_plan_destroy(P); return e; }
-        P->s2_wg_direct = true;
-      }
-    }
+  int e;
+  if ((e = upload(P->wg_pair_off, &P->d_pair_off)) || (e = upload(P->wg_uitems, &P->d_uitems))) return e;
+  if (hipMalloc((void**)&P->d_part, (size_t)nsplit * off * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
+  if (hipMalloc((void**)&P->d_cspart, (size_t)nsplit * P->N * P->Cout * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
+  return 0;
+}
+
+// Both directions of a factor-2 layer on the phase kernels, or neither: channel counts or a geometry they do not serve (UNSUPPORTED) leave
+// the plan on its other routes.  gd, gh, gw: the coarse grid.
+int phase_sides_create(mi_conv_plan* P, PhaseKind kind_fwd, int mode_fwd, PhaseKind kind_dg, int mode_dg, int gd, int gh, int gw) {
+  static const int use_ph = env_int("MI_CONVPH", 1);
+  if (!use_ph || (P->Cin % 8) != 0 || (P->Cout % 8) != 0) return 0;
+  int e = phase_side_create(P->ph_fwd, kind_fwd, mode_fwd, 0, P->Cout, P->Cin, gd, gh, gw, P->N);
+  if (!e) e = phase_side_create(P->ph_dg, kind_dg, mode_dg, 1, P->Cin, P->Cout, gd, gh, gw, P->N);
+  if (e) { phase_side_free(P->ph_fwd); phase_side_free(P->ph_dg); }
+  return e == MI_ERR_UNSUPPORTED ? 0 : e;
+}
+
+// k3 s2 p1 on all three axes: forward and data gradient on the phase kernels (no space-to-depth copies of x / dx)
+int conv_plan_s2_phase(mi_conv_plan* P) {
+  bool s2all = P->Di > 1;
+  for (int a = 0; a < 3; ++a) s2all = s2all && P->k[a] == 3 && P->s[a] == 2 && P->p[a] == 1;
+  if (!s2all) return 0;
+  if (int e = phase_sides_create(P, S2_FWD, 2, S2_DG, 1, P->Do, P->Ho, P->Wo)) return e;
+  if (!P->ph_fwd.mode || (P->Cin % 32) != 0) return 0;
+  // weight gradient: the class images are gathered from x in place (k_conv_wgrad2, sx = 2)
+  std::vector<int> h2 = P->wg.hdr;
+  const int cpq = P->Cin / 32;  // chunks per class
+  for (int pr = 0; pr < P->wg.ny * P->wg.nchunks; ++pr) {
+    const int ch = pr % P->wg.nchunks, q = ch / cpq;
+    h2[(size_t)pr * 4 + 2] = (ch % cpq) * 32;
+    h2[(size_t)pr * 4 + 3] = q;  // (qd, qh, qw) = bits 2, 1, 0: all three factors are 2
   }
-  if (P->strided) {
+  if (int e = upload(h2, &P->d_hdr2)) return e;
+  P->s2_wg_direct = true;
+  return 0;
+}
+
+int conv_plan_init(mi_conv_plan* P, int N, int Di, int Hi, int Wi, int Cin, int Cout, const int* k, const int* s, const int* p) {
+  P->N = N; P->Di = Di; P->Hi = Hi; P->Wi = Wi; P->Cin = Cin; P->Cout = Cout;
+  std::vector<AxisCombo> cf[3], cdg[3];
+  int dims[3] = {Di, Hi, Wi}, od[3], halo_f[3] = {0, 0, 0}, halo_d[3] = {0, 0, 0};
+  for (int a = 0; a < 3; ++a) {
+    P->k[a] = k[a]; P->s[a] = s[a]; P->p[a] = p[a];
+    if (!axis_combos_fwd(k[a], s[a], p[a], cf[a], P->f[a]) || !axis_combos_dgrad(k[a], s[a], p[a], cdg[a])) return MI_ERR_UNSUPPORTED;
+    od[a] = (dims[a] + 2 * p[a] - k[a]) / s[a] + 1;
+    for (auto& c : cf[a]) if (c.delta != 0) halo_f[a] = 1;
+    for (auto& c : cdg[a]) if (c.delta != 0) halo_d[a] = 1;
+  }
+  P->Do = od[0]; P->Ho = od[1]; P->Wo = od[2];
+  P->Q = P->f[0] * P->f[1] * P->f[2];
+  P->strided = P->Q > 1;
+  P->Dp = (Di + P->f[0] - 1) / P->f[0]; P->Hp = (Hi + P->f[1] - 1) / P->f[1]; P->Wp = (Wi + P->f[2] - 1) / P->f[2];
+  P->KT = k[0] * k[1] * k[2];
+  int e;
+  if ((e = conv_plan_routes(P, halo_f, halo_d))) return e;
+  build_tables(P->fwd, P->g_fwd, P->ncb_fwd, cf, P->f, P->k, true, Cin, Cout, false, P->v27_fwd || P->v11_fwd);
+  build_tables(P->dg, P->g_dg, P->ncb_dg, cdg, P->f, P->k, false, Cout, Cin, true, P->v27_dg || P->v11_dg);
+  build_tables(P->wg, P->g_wg, 1, cf, P->f, P->k, true, Cin, Cout, false);  // (NCB = 1; weights unused)
+  if ((e = upload_tables(P->fwd, true)) || (e = upload_tables(P->dg, true)) || (e = upload_tables(P->wg, false))) return e;
+  if ((e = conv_plan_wgrad_slabs(P)) || (e = conv_plan_s2_phase(P))) return e;
+  if (P->strided) {  // space-to-depth images of x and dx
     size_t nb = (size_t)N * P->Dp * P->Hp * P->Wp * P->Q * Cin * 2;
-    if (hipMalloc((void**)&P->d_xs, nb) != hipSuccess || hipMalloc((void**)&P->d_dxs, nb) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
+    if (hipMalloc((void**)&P->d_xs, nb) != hipSuccess || hipMalloc((void**)&P->d_dxs, nb) != hipSuccess) return (int)hipErrorOutOfMemory;
   }
+  return 0;
+}
+
+int upconv_plan_init(mi_conv_plan* P, int N, int D, int H, int W, int Cin, int Cout) {
+  P->up = true;
+  P->N = N; P->Di = D; P->Hi = H; P->Wi = W; P->Cin = Cin; P->Cout = Cout;
+  P->Do = 2 * D; P->Ho = 2 * H; P->Wo = 2 * W;
+  for (int a = 0; a < 3; ++a) { P->k[a] = 3; P->s[a] = 1; P->p[a] = 1; P->f[a] = 1; }
+  P->Q = 1; P->KT = 27; P->Dp = D; P->Hp = H; P->Wp = W;
+  const int k3[3] = {3, 3, 3}, s1[3] = {1, 1, 1}, p1[3] = {1, 1, 1};
+  if (int e = mi_conv_plan_create(&P->up_inner, N, 2 * D, 2 * H, 2 * W, Cin, Cout, k3, s1, p1)) return e;  // (the fallback's plan and buffer)
+  if (hipMalloc((void**)&P->d_xup, (size_t)N * 8 * D * H * W * Cin * 2) != hipSuccess) return (int)hipErrorOutOfMemory;
+  if (int e = phase_sides_create(P, UC_FWD, 1, UC_DG, 2, D, H, W)) return e;
+  if (P->ph_fwd.mode) {
+    const int ew = upconv_wgrad_tables(P);
+    if (ew && ew != MI_ERR_UNSUPPORTED) return ew;
+    P->up_wg = ew == 0;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_conv_plan_create(mi_conv_plan** out, int N, int Di, int Hi, int Wi, int Cin, int Cout, const int* k, const int* s, const int* p) {
+  if (!out || N <= 0 || Di <= 0 || Hi <= 0 || Wi <= 0 || Cin <= 0 || Cout <= 0) return MI_ERR_BAD_ARG;
+  mi_conv_plan* P = new mi_conv_plan();
+  if (int e = conv_plan_init(P, N, Di, Hi, Wi, Cin, Cout, k, s, p)) { mi_conv_plan_destroy(P); return e; }
   *out = P;
   return 0;
 }
@@ -2536,26 +2626,7 @@ int mi_upconv_plan_create(mi_conv_plan** out, int N, int D, int H, int W, int Ci
   if (!out || N <= 0 || D <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return MI_ERR_BAD_ARG;
   if (D == 1) return MI_ERR_UNSUPPORTED;  // 2-D nets: upsample kernel + plain conv (engine.upsample)
   mi_conv_plan* P = new mi_conv_plan();
-  P->up = true;
-  P->N = N; P->Di = D; P->Hi = H; P->Wi = W; P->Cin = Cin; P->Cout = Cout;
-  P->Do = 2 * D; P->Ho = 2 * H; P->Wo = 2 * W;
-  for (int a = 0; a < 3; ++a) { P->k[a] = 3; P->s[a] = 1; P->p[a] = 1; P->f[a] = 1; }
-  P->Q = 1; P->KT = 27; P->Dp = D; P->Hp = H; P->Wp = W;
-  const int k3[3] = {3, 3, 3}, s1[3] = {1, 1, 1}, p1[3] = {1, 1, 1};
-  int e = mi_conv_plan_create(&P->up_inner, N, 2 * D, 2 * H, 2 * W, Cin, Cout, k3, s1, p1);
-  if (e) { P->up_inner = nullptr; mi_conv_plan_destroy(P); return e; }
-  if (hipMalloc((void**)&P->d_xup, (size_t)N * 8 * D * H * W * Cin * 2) != hipSuccess) { mi_conv_plan_destroy(P); return (int)hipErrorOutOfMemory; }
-  static const int use_ph = env_int("MI_CONVPH", 1);
-  if (use_ph && (Cin % 8) == 0 && (Cout % 8) == 0) {
-    int e1 = phase_side_create(P->ph_fwd, UC_FWD, 1, 0, Cout, Cin, D, H, W, N);
-    int e2 = e1 ? e1 : phase_side_create(P->ph_dg, UC_DG, 2, 1, Cin, Cout, D, H, W, N);
-    if (e1 || e2) { phase_side_free(P->ph_fwd); phase_side_free(P->ph_dg); if ((e1 ? e1 : e2) != MI_ERR_UNSUPPORTED) { mi_conv_plan_destroy(P); return e1 ? e1 : e2; } }
-    if (P->ph_fwd.mode) {
-      const int ew = upconv_wgrad_tables(P);
-      if (ew && ew != MI_ERR_UNSUPPORTED) { mi_conv_plan_destroy(P); return ew; }
-      P->up_wg = ew == 0;
-    }
-  }
+  if (int e = upconv_plan_init(P, N, D, H, W, Cin, Cout)) { mi_conv_plan_destroy(P); return e; }
   *out = P;
   return 0;
 }
@@ -2736,9 +2807,10 @@ int mi_conv_pack_batch_create(mi_pack_batch** out, mi_conv_plan* const* plans, c
   B->ng11 = (int)g11.size(); B->g11_blocks = g11_nblocks;
   if (use_super > 1) fprintf(stderr, "[pack batch] %d plans, %zu groups, %zu super-groups, paired: %d, LDS %zu B\n", n, groups.size(), supers.size(), (int)super_ok, lds_super);
   if (super_ok && !supers.empty() && lds_super <= 150 * 1024) {
+    bool lds_raised = false;  // (per batch, as before the helper)
     if (hipMalloc((void**)&B->d_supers, sizeof(PackSuper) * supers.size()) != hipSuccess ||
         hipMemcpy(B->d_supers, supers.data(), sizeof(PackSuper) * supers.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipFuncSetAttribute((const void*)k_pack_super, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+        raise_lds_limit((const void*)k_pack_super, lds_raised) != 0) {
       mi_conv_pack_batch_destroy(B);
       return (int)hipErrorOutOfMemory;
     }
@@ -2796,6 +2868,40 @@ int mi_conv_fwd_stats_chunks(const mi_conv_plan* P) {
   return 4 * mi_conv27_grid_x(P->N * P->g_fwd.tilesD * P->g_fwd.tilesH * P->g_fwd.tilesW, P->fwd.ny);
 }
 
+// ---- routes of mi_conv_fwd that are more than one launch call, in the order the entry point tries them
+// Upsample + conv, fallback: materialise the nearest-upsampled tensor, plain k3 s1 conv on the fine grid
+static int fwd_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
+                               const void* res, int res_cs, void* y, int y_cs, hipStream_t st) {
+  if (x_cs != P->Cin) return MI_ERR_UNSUPPORTED;
+  if (int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st)) return e;
+  return mi_conv_fwd(P->up_inner, P->d_xup, P->Cin, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, nullptr, st);
+}
+// arguments of the three tiled kernels (1x1 streaming, conv27, table-driven); a strided conv reads the space-to-depth image of x, made here
+static int fwd_args(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
+                    const void* res, int res_cs, void* y, int y_cs, ConvArgs& a, int& ntiles, hipStream_t st) {
+  memset(&a, 0, sizeof(a));
+  a.x = (const bf16*)x; a.x_cs = x_cs; a.N = P->N; a.Di = P->Di; a.Hi = P->Hi; a.Wi = P->Wi; a.Cin = P->Cin;
+  if (P->strided) {
+    if (int e = mi_space_to_depth(x, x_cs, P->d_xs, P->N, P->Di, P->Hi, P->Wi, P->Cin, P->f[0], P->f[1], P->f[2], st)) return e;
+    a.x = P->d_xs; a.x_cs = a.Cin = P->Q * P->Cin; a.Di = P->Dp; a.Hi = P->Hp; a.Wi = P->Wp;
+  }
+  a.y = (bf16*)y; a.y_cs = y_cs; a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
+  a.ogpq = P->fwd.ny; a.outc_q = P->Cout;
+  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
+  a.addvec = addvec; a.addvec_stride = addvec_stride;
+  a.res = (const bf16*)res; a.res_cs = res_cs;
+  a.perm16 = P->v27_fwd || P->v11_fwd;
+  return conv_args_tables(a, P->fwd, P->g_fwd, ntiles);
+}
+// conv27.hip.  Leaves its byte spans in `a`: after UNSUPPORTED (odd output pitch / >= 4 GiB output; the caller falls through only without
+// out_stats) the table-driven kernel runs with them
+static int fwd_conv27(mi_conv_plan* P, ConvArgs& a, int ntiles, float* out_stats, hipStream_t st) {
+  a.res_bytes = a.res ? span32(P->N, P->Do, P->Ho, P->Wo, a.res_cs) : 0u;  // (0: unbounded, both)
+  a.y_bytes = span32(P->N, P->Do, P->Ho, P->Wo, a.y_cs);
+  a.stats = out_stats; a.stats_chunks = out_stats ? mi_conv_fwd_stats_chunks(P) : 0;
+  return mi_launch_conv27(a, P->ncb_fwd, 0, ntiles, P->fwd.ny, st);
+}
+
 int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
                 const void* res, int res_cs, void* y, int y_cs, float* out_stats, hipStream_t st) {
   if (!P || !x || !y || x_cs < P->Cin || y_cs < P->Cout) return MI_ERR_BAD_ARG;
@@ -2804,86 +2910,41 @@ int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shi
     const int e = phase_side_run(P->ph_fwd, x, x_cs, P->Di, P->Hi, P->Wi, y, y_cs, P->Do, P->Ho, P->Wo, P->N, addvec, addvec_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  if (P->up) {  // fallback: materialise the nearest-upsampled tensor, plain k3 s1 conv on the fine grid
-    if (x_cs != P->Cin) return MI_ERR_UNSUPPORTED;
-    int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st);
-    if (e) return e;
-    return mi_conv_fwd(P->up_inner, P->d_xup, P->Cin, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, nullptr, st);
-  }
-  if ((P->c1_in || P->c1_out) && P->c1_packed && !scale_shift && !res) {
+  if (P->up) return fwd_upconv_fallback(P, x, x_cs, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, st);
+  if ((P->c1_in || P->c1_out) && P->c1_packed && !scale_shift && !res) {  // one channel on one side (conv_c1.hip)
     if (out_stats && !P->c1_in) return MI_ERR_UNSUPPORTED;
-    int e = P->c1_in ? mi_launch_c1_expand(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st, out_stats)
-                     : mi_launch_c1_reduce(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cin, st);
+    const int e = P->c1_in ? mi_launch_c1_expand(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st, out_stats)
+                           : mi_launch_c1_reduce(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cin, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
   if (out_stats && P->c1_in) return MI_ERR_UNSUPPORTED;  // (the table-driven fallback of a single-channel conv emits no sums: never silently)
   ConvArgs a;
-  memset(&a, 0, sizeof(a));
-  const bf16* src = (const bf16*)x;
-  int src_cs = x_cs;
-  if (P->strided) {
-    int e = mi_space_to_depth(x, x_cs, P->d_xs, P->N, P->Di, P->Hi, P->Wi, P->Cin, P->f[0], P->f[1], P->f[2], st);
-    if (e) return e;
-    src = P->d_xs;
-    src_cs = P->Q * P->Cin;
-  }
-  a.x = src; a.x_cs = src_cs; a.N = P->N; a.Di = P->Dp; a.Hi = P->Hp; a.Wi = P->Wp; a.Cin = P->strided ? P->Q * P->Cin : P->Cin;
-  if (!P->strided) { a.Di = P->Di; a.Hi = P->Hi; a.Wi = P->Wi; }
-  a.y = (bf16*)y; a.y_cs = y_cs; a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
-  a.ogpq = P->fwd.ny; a.outc_q = P->Cout;
-  a.wpk = P->fwd.d_wpk; a.hdr = P->fwd.d_hdr; a.taps = P->fwd.d_taps; a.nchunks = P->fwd.nchunks;
-  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
-  a.addvec = addvec; a.addvec_stride = addvec_stride;
-  a.res = (const bf16*)res; a.res_cs = res_cs;
-  a.g = P->g_fwd;
-  int ntiles = P->N * a.g.tilesD * a.g.tilesH * a.g.tilesW;
-  a.wpk_bytes = (unsigned)P->fwd.nfrags * 1024u;
-  {
-    int64_t xb = (int64_t)a.N * a.Di * a.Hi * a.Wi * a.x_cs * 2;
-    if (xb >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
-    a.x_bytes = (unsigned)xb;
-  }
-  a.perm16 = P->v27_fwd || P->v11_fwd;
+  int ntiles;
+  if (int e = fwd_args(P, x, x_cs, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, a, ntiles, st)) return e;
   if (P->g11 && !P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0 && (y_cs & 7) == 0 && addvec_stride == 0 && !out_stats &&
-      ((uintptr_t)x & 15) == 0 && (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // y[vox][co] = x[vox][:] . W[co][:] + bias
+      ((uintptr_t)x & 15) == 0 && (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // 1x1 on the NT GEMM: y[vox][co] = x[vox][:] . W[co][:] + bias
     return mi_gemm_nt_bf16(x, x_cs, 0, 0, P->d_w11, P->Cin, 0, 0, y, y_cs, 0, 0, addvec, nullptr, 0, 0, 0, P->N * P->Do * P->Ho * P->Wo, P->Cout, P->Cin, 1, 1,
                            1.0f, 0, 0, st);
-  if (P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0) {
-    const int64_t yb = (int64_t)P->N * P->Do * P->Ho * P->Wo * y_cs * 2;
-    a.y_bytes = yb < (1ll << 32) ? (unsigned)yb : 0u;
+  if (P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
+    a.y_bytes = span32(P->N, P->Do, P->Ho, P->Wo, y_cs);  // (0: unbounded)
     return mi_launch_conv1x1(a, P->ncb_fwd, P->fwd.ny, st);
   }
   if (P->v27_fwd && !scale_shift) {  // (the fused GroupNorm prologue lives in the register-staged kernel)
     if (x_cs & 7) return MI_ERR_UNSUPPORTED;
-    const int64_t rb = res ? (int64_t)P->N * P->Do * P->Ho * P->Wo * res_cs * 2 : 0;
-    a.res_bytes = rb < (1ll << 32) ? (unsigned)rb : 0u;
-    const int64_t yb = (int64_t)P->N * P->Do * P->Ho * P->Wo * y_cs * 2;
-    a.y_bytes = yb < (1ll << 32) ? (unsigned)yb : 0u;
-    a.stats = out_stats; a.stats_chunks = out_stats ? mi_conv_fwd_stats_chunks(P) : 0;
-    const int e27 = mi_launch_conv27(a, P->ncb_fwd, 0, ntiles, P->fwd.ny, st);
-    if (e27 != MI_ERR_UNSUPPORTED || out_stats) return e27;  // (odd output pitch / >= 4 GiB output: the table-driven kernel below)
-    a.stats = nullptr;
+    const int e = fwd_conv27(P, a, ntiles, out_stats, st);
+    if (e != MI_ERR_UNSUPPORTED || out_stats) return e;
   }
   return launch_igemm_any(a, P->ncb_fwd, P->full27 ? 1 : 0, ntiles, P->fwd.ny, st);
 }
 
-int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_cs, hipStream_t st) {
-  if (!P || !dy || !dx || dy_cs < P->Cout || dx_cs < P->Cin) return MI_ERR_BAD_ARG;
-  if (P->ph_dg.mode) {  // data gradient of Upsample + conv (gather from the fine dy) / of the k3 s2 conv (scatter into the fine dx)
-    const int e = phase_side_run(P->ph_dg, dy, dy_cs, P->Do, P->Ho, P->Wo, dx, dx_cs, P->Di, P->Hi, P->Wi, P->N, nullptr, 0, st);
-    if (e != MI_ERR_UNSUPPORTED) return e;
-  }
-  if (P->up) {  // fallback: data gradient on the fine grid, then fold the 2x2x2 blocks (nearest-upsample backward)
-    if (dx_cs != P->Cin) return MI_ERR_UNSUPPORTED;
-    int e = mi_conv_dgrad(P->up_inner, dy, dy_cs, P->d_xup, P->Cin, st);
-    if (e) return e;
-    return mi_upsample_nearest_bwd(P->d_xup, dx, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st);
-  }
-  if (P->c1_out && P->c1_packed) {  // dx[v][ci] = sum_t dy[v - t] W[0][ci][t]: the 1 -> C kernel with the taps flipped
-    int e = mi_launch_c1_expand(dy, dy_cs, P->d_c1w, nullptr, 0, dx, dx_cs, P->N, P->Di, P->Hi, P->Wi, P->Cin, 1, st);
-    if (e != MI_ERR_UNSUPPORTED) return e;
-  }
-  ConvArgs a;
+// Upsample + conv, fallback: data gradient on the fine grid, then fold the 2x2x2 blocks (nearest-upsample backward)
+static int dgrad_upconv_fallback(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_cs, hipStream_t st) {
+  if (dx_cs != P->Cin) return MI_ERR_UNSUPPORTED;
+  if (int e = mi_conv_dgrad(P->up_inner, dy, dy_cs, P->d_xup, P->Cin, st)) return e;
+  return mi_upsample_nearest_bwd(P->d_xup, dx, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st);
+}
+// arguments of the three tiled kernels: dy is their input; a strided conv's kernel writes the depth image of dx (folded by the caller)
+static int dgrad_args(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_cs, ConvArgs& a, int& ntiles) {
   memset(&a, 0, sizeof(a));
   a.x = (const bf16*)dy; a.x_cs = dy_cs; a.N = P->N; a.Di = P->Do; a.Hi = P->Ho; a.Wi = P->Wo; a.Cin = P->Cout;
   a.Do = P->Dp; a.Ho = P->Hp; a.Wo = P->Wp;
@@ -2895,35 +2956,142 @@ int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_c
   } else {
     a.y = (bf16*)dx; a.y_cs = dx_cs;
   }
-  a.wpk = P->dg.d_wpk; a.hdr = P->dg.d_hdr; a.taps = P->dg.d_taps; a.nchunks = P->dg.nchunks;
-  a.g = P->g_dg;
-  int ntiles = P->N * a.g.tilesD * a.g.tilesH * a.g.tilesW;
-  a.wpk_bytes = (unsigned)P->dg.nfrags * 1024u;
-  {
-    int64_t xb = (int64_t)a.N * a.Di * a.Hi * a.Wi * a.x_cs * 2;
-    if (xb >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
-    a.x_bytes = (unsigned)xb;
-  }
   a.perm16 = P->v27_dg || P->v11_dg;
+  return conv_args_tables(a, P->dg, P->g_dg, ntiles);
+}
+
+int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_cs, hipStream_t st) {
+  if (!P || !dy || !dx || dy_cs < P->Cout || dx_cs < P->Cin) return MI_ERR_BAD_ARG;
+  if (P->ph_dg.mode) {  // data gradient of Upsample + conv (gather from the fine dy) / of the k3 s2 conv (scatter into the fine dx)
+    const int e = phase_side_run(P->ph_dg, dy, dy_cs, P->Do, P->Ho, P->Wo, dx, dx_cs, P->Di, P->Hi, P->Wi, P->N, nullptr, 0, st);
+    if (e != MI_ERR_UNSUPPORTED) return e;
+  }
+  if (P->up) return dgrad_upconv_fallback(P, dy, dy_cs, dx, dx_cs, st);
+  if (P->c1_out && P->c1_packed) {  // dx[v][ci] = sum_t dy[v - t] W[0][ci][t]: the 1 -> C kernel with the taps flipped
+    const int e = mi_launch_c1_expand(dy, dy_cs, P->d_c1w, nullptr, 0, dx, dx_cs, P->N, P->Di, P->Hi, P->Wi, P->Cin, 1, st);
+    if (e != MI_ERR_UNSUPPORTED) return e;
+  }
+  ConvArgs a;
+  int ntiles;
+  if (int e = dgrad_args(P, dy, dy_cs, dx, dx_cs, a, ntiles)) return e;
   if (P->g11 && !P->v11_dg && (dy_cs & 7) == 0 && (dx_cs & 7) == 0 && ((uintptr_t)dy & 15) == 0 &&
-      (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // dx[vox][ci] = dy[vox][:] . W^T[ci][:]
+      (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // 1x1 on the NT GEMM: dx[vox][ci] = dy[vox][:] . W^T[ci][:]
     return mi_gemm_nt_bf16(dy, dy_cs, 0, 0, P->d_w11t, P->Cout, 0, 0, dx, dx_cs, 0, 0, nullptr, nullptr, 0, 0, 0, P->N * P->Do * P->Ho * P->Wo, P->Cin, P->Cout, 1,
                            1, 1.0f, 0, 0, st);
-  if (P->v11_dg && (dy_cs & 7) == 0) {
-    const int64_t yb = (int64_t)P->N * a.Do * a.Ho * a.Wo * a.y_cs * 2;
-    a.y_bytes = yb < (1ll << 32) ? (unsigned)yb : 0u;
+  if (P->v11_dg && (dy_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
+    a.y_bytes = span32(P->N, a.Do, a.Ho, a.Wo, a.y_cs);  // (0: unbounded)
     return mi_launch_conv1x1(a, P->ncb_dg, P->dg.ny, st);
   }
-  if (P->v27_dg) {
+  if (P->v27_dg) {  // conv27.hip
     if (dy_cs & 7) return MI_ERR_UNSUPPORTED;
-    const int64_t yb = (int64_t)P->N * a.Do * a.Ho * a.Wo * a.y_cs * 2;
-    a.y_bytes = yb < (1ll << 32) ? (unsigned)yb : 0u;
-    const int e27 = mi_launch_conv27(a, P->ncb_dg, 1, ntiles, P->dg.ny, st);
-    if (e27 != MI_ERR_UNSUPPORTED) return e27;
+    a.y_bytes = span32(P->N, a.Do, a.Ho, a.Wo, a.y_cs);  // (0: unbounded; stays set for the table-driven kernel after UNSUPPORTED)
+    const int e = mi_launch_conv27(a, P->ncb_dg, 1, ntiles, P->dg.ny, st);
+    if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  int e = launch_igemm_any(a, P->ncb_dg, P->full27 ? 2 : 0, ntiles, P->dg.ny, st);
-  if (e) return e;
+  if (int e = launch_igemm_any(a, P->ncb_dg, P->full27 ? 2 : 0, ntiles, P->dg.ny, st)) return e;
   if (P->strided) return mi_depth_to_space(P->d_dxs, dx, P->N, P->Di, P->Hi, P->Wi, P->Cin, P->f[0], P->f[1], P->f[2], st);
+  return 0;
+}
+
+// Upsample + conv, fallback: on the fine grid against the nearest-upsampled x
+static int wgrad_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, const void* dy, int dy_cs, float* dw,
+                                 float* dy_colsum, int dy_colsum_stride, hipStream_t st) {
+  if (x_cs != P->Cin || scale_shift) return MI_ERR_UNSUPPORTED;
+  if (int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st)) return e;
+  return mi_conv_wgrad(P->up_inner, P->d_xup, P->Cin, nullptr, 0, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
+}
+// Arguments of the tiled weight-gradient kernels, and which of the two families runs: `dma` = the LDS-DMA kernels (launch_wgrad_dma: whole
+// 8-channel pieces only, no fused prologue), else the register-staged ones (launch_wgrad_regs).  A k3 s2 conv on all axes has the LDS-DMA
+// kernel gather each pair's class image from x in place (`direct`: d_hdr2, sx = 2 -- no space-to-depth copy); the register-staged kernel
+// understands neither, so direct => dma.  Every other strided conv reads the space-to-depth image of x, made here.
+static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const void* dy, int dy_cs, float* dy_colsum,
+                      int dy_colsum_stride, WgradArgs& w, bool& dma, bool& direct, hipStream_t st) {
+  memset(&w, 0, sizeof(w));
+  ConvArgs& a = w.c;
+  const Geom& g = P->g_wg;
+  static const int use_w2 = env_int("MI_WGRAD2", 1);
+  const int nvox = g.TD * g.TH * g.TW, px = (g.lds_bytes + 1023) / 1024, py = (nvox * 64 + 1023) / 1024;
+  const unsigned dyb = span32(P->N, P->Do, P->Ho, P->Wo, dy_cs);
+  const bool dma_ok = use_w2 && !scale_shift && g.vox == 64 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && px <= 40 && py <= 16 && dyb;
+  direct = P->s2_wg_direct && dma_ok && (x_cs & 7) == 0 && span32(P->N, P->Di, P->Hi, P->Wi, x_cs);
+  const bool s2d = P->strided && !direct;
+  a.x = s2d ? P->d_xs : (const bf16*)x; a.x_cs = s2d ? P->Q * P->Cin : x_cs; a.N = P->N;
+  a.Di = s2d ? P->Dp : P->Di; a.Hi = s2d ? P->Hp : P->Hi; a.Wi = s2d ? P->Wp : P->Wi;
+  a.Cin = s2d ? P->Q * P->Cin : P->Cin;
+  dma = dma_ok && (a.x_cs & 7) == 0 && (a.Cin & 7) == 0;
+  if (direct && !dma) return MI_ERR_BAD_ARG;
+  if (s2d)
+    if (int e = mi_space_to_depth(x, x_cs, P->d_xs, P->N, P->Di, P->Hi, P->Wi, P->Cin, P->f[0], P->f[1], P->f[2], st)) return e;
+  a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
+  a.hdr = direct ? P->d_hdr2 : P->wg.d_hdr; a.taps = P->wg.d_taps; a.nchunks = P->wg.nchunks;
+  w.sx = direct ? 2 : 1; w.sy = 1; w.cs_chunks = 1;
+  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
+  if (!(a.x_bytes = span32(a.N, a.Di, a.Hi, a.Wi, a.x_cs))) return MI_ERR_UNSUPPORTED;
+  a.g = g;
+  w.dy = (const bf16*)dy; w.dy_cs = dy_cs; w.dy_bytes = dma ? dyb : 0u;
+  w.part = P->d_part; w.pair_off = P->d_pair_off; w.split_stride = P->wg_split_stride;
+  w.ntiles = P->N * g.tilesD * g.tilesH * g.tilesW; w.nsplit = P->wg_nsplit; w.npairs = P->wg.ny * P->wg.nchunks;
+  w.contig = wgrad_contig(w.ntiles, w.nsplit);
+  static const int dbg = mi_diag_knob("MI_WGRAD_DBG"); w.dbg = dbg;
+  w.colsum = dy_colsum; w.colsum_stride = dy_colsum_stride;
+  static const int cs_slab = env_int("MI_CS_SLAB", 1);
+  bool cs_pairs_multi_tap = true;  // pairs that own the column sums (first chunk of a cout block) must be tap pairs, not k-split pairs
+  for (int yy = 0; yy < P->wg.ny; ++yy) cs_pairs_multi_tap = cs_pairs_multi_tap && P->wg.hdr[((size_t)yy * P->wg.nchunks) * 4 + 1] > 1;
+  w.cs_part = (cs_slab && dy_colsum && cs_pairs_multi_tap) ? P->d_cspart : nullptr;
+  if (dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout) return MI_ERR_BAD_ARG;  // 0: one row for the whole batch
+  if ((g.TD * (g.TH / 2) * (g.TW / 8)) % 2) return MI_ERR_BAD_ARG;  // the k loop is unrolled in pairs
+  if ((nvox * 4 + 255) / 256 > 4 || (g.HD * g.HH * g.HW * 4 + 255) / 256 > 16) return MI_ERR_BAD_ARG;  // (256-thread piece counts; the kernels run 512 threads: half of each)
+  int max_taps = 0;
+  for (size_t i = 1; i < P->wg.hdr.size(); i += 4) max_taps = P->wg.hdr[i] > max_taps ? P->wg.hdr[i] : max_taps;
+  if (max_taps >= 32) return MI_ERR_UNSUPPORTED;  // wave 7 keeps a spare accumulator for the fused dY column sums
+  return 0;
+}
+// k_conv_wgrad3 (k3 s1, rolling x halo) / k_conv_wgrad2<GEO3D>
+static int launch_wgrad_dma(const mi_conv_plan* P, WgradArgs& w, bool direct, hipStream_t st) {
+  const Geom& g = w.c.g;
+  const int px = (g.lds_bytes + 1023) / 1024, py = (g.TD * g.TH * g.TW * 64 + 1023) / 1024;
+  w.nbuf = (P->KT == 1 && px == 16 && py == 16) ? 4 : 2;  // 1x1: tiles are pure loads -> three tiles in flight per workgroup
+  static const int use_flags = env_int("MI_WGRAD_FLAGS", 1); w.flags = use_flags;
+  const size_t lds2 = (size_t)(w.nbuf * (px + py)) * 1024 + 64;  // + the hand-off counters
+  const bool geo3 = P->full27 && g.row == WG3_XROW && g.slice == WG3_XSLICE && g.TD == 4 && g.TH == 8 && g.TW == 8;
+  static bool raised3 = false, raisedg = false, raisedr = false;
+  if (int e = geo3 ? raise_lds_limit((const void*)k_conv_wgrad2<true>, raised3) : raise_lds_limit((const void*)k_conv_wgrad2<false>, raisedg)) return e;
+  static const int use_roll = env_int("MI_WGRAD_ROLL", 1);  // 0: k_conv_wgrad2 for every layer (A/B runs)
+  // (runs of more than two columns lose more to L2 locality -- the workgroups of an XCD are then columns apart -- than the saved
+  // pieces return: 64->64 and 96->32 at 128^3 measured +1 / +2.5 %, 32->32 -6 %, 64->32 -3.5 %, the 64^3 .. 16^3 levels -1.5 .. -3 %)
+  const bool roll = use_roll && geo3 && !direct && w.sx == 1 && w.sy == 1 && w.nbuf == 2 && w.flags && P->wg.hdr[1] == 27 && w.nsplit <= w.ntiles &&
+                    g.tilesD >= 2 && (use_roll > 1 || (int64_t)w.ntiles <= 2ll * g.tilesD * w.nsplit);
+  const dim3 grid(wgrad_grid(w.npairs, w.nsplit));
+  if (roll) {
+    if (int e = raise_lds_limit((const void*)k_conv_wgrad3, raisedr)) return e;
+    wg3_diag_arm();
+    hipLaunchKernelGGL(k_conv_wgrad3, grid, dim3(768), (size_t)WR_LDS, st, w);
+    wg3_diag_report(P->Cin, P->Cout, w.ntiles, w.nsplit, grid.x);
+  } else if (geo3) hipLaunchKernelGGL(k_conv_wgrad2<true>, grid, dim3(768), lds2, st, w);
+  else hipLaunchKernelGGL(k_conv_wgrad2<false>, grid, dim3(768), lds2, st, w);
+  wg2_diag_report();
+  return 0;
+}
+// k_conv_wgrad<NP, 2, GEO3D>: NP 16-byte halo pieces per thread
+static int launch_wgrad_regs(const mi_conv_plan* P, const WgradArgs& w, hipStream_t st) {
+  const Geom& g = w.c.g;
+  const size_t lds = (size_t)g.lds_bytes + (size_t)g.TD * g.TH * g.TW * g.vox;
+  const dim3 grid(wgrad_grid(w.npairs, w.nsplit)), blk(512);
+#define MI_LAUNCH_WG(NPV, G3)                                                 \
+  do {                                                                        \
+    auto kern = k_conv_wgrad<NPV, 2, G3>;                                     \
+    static bool raised = false;                                               \
+    if (int e = raise_lds_limit((const void*)kern, raised)) return e;         \
+    hipLaunchKernelGGL(kern, grid, blk, lds, st, w);                          \
+  } while (0)
+  const int np8 = (g.HD * g.HH * g.HW * 4 + 511) / 512;
+  const bool geo3d = P->full27 && g.vox == 64 && g.row == WG3_XROW && g.slice == WG3_XSLICE && g.TD == 4 && g.TH == 8 && g.TW == 8 && np8 == 5;
+  if (geo3d) MI_LAUNCH_WG(5, true);
+  else if (np8 <= 2) MI_LAUNCH_WG(2, false);
+  else if (np8 <= 3) MI_LAUNCH_WG(3, false);
+  else if (np8 <= 5) MI_LAUNCH_WG(5, false);
+  else MI_LAUNCH_WG(8, false);
+#undef MI_LAUNCH_WG
   return 0;
 }
 
@@ -2931,200 +3099,30 @@ int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_c
 int mi_conv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const void* dy, int dy_cs, float* dw,
                   float* dy_colsum, int dy_colsum_stride, hipStream_t st) {
   if (!P || !x || !dy || !dw || x_cs < P->Cin || dy_cs < P->Cout) return MI_ERR_BAD_ARG;
-  if (P->up && P->up_wg && !scale_shift && (x_cs & 7) == 0 && (dy_cs & 7) == 0) {
+  if (P->up && P->up_wg && !scale_shift && (x_cs & 7) == 0 && (dy_cs & 7) == 0) {  // Upsample + conv by phase pairs on the coarse grid
     const int e = upconv_wgrad(P, x, x_cs, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  if (P->up) {  // fallback: on the fine grid against the nearest-upsampled x
-    if (x_cs != P->Cin || scale_shift) return MI_ERR_UNSUPPORTED;
-    int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st);
-    if (e) return e;
-    return mi_conv_wgrad(P->up_inner, P->d_xup, P->Cin, nullptr, 0, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
-  }
+  if (P->up) return wgrad_upconv_fallback(P, x, x_cs, scale_shift, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
   static const int use_w11 = env_int("MI_WGRAD1X1", 1);
   if (use_w11 && P->KT == 1 && !P->strided && !scale_shift && !(dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout)) {
-    int e = mi_launch_wgrad1x1(x, x_cs, P->Cin, dy, dy_cs, P->Cout, P->N, (int64_t)P->Di * P->Hi * P->Wi, dw, dy_colsum, dy_colsum_stride, st);
+    const int e = mi_launch_wgrad1x1(x, x_cs, P->Cin, dy, dy_cs, P->Cout, P->N, (int64_t)P->Di * P->Hi * P->Wi, dw, dy_colsum, dy_colsum_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
   static const int use_c1w = env_int("MI_C1_WGRAD", 1);
   if (use_c1w && (P->c1_in || P->c1_out) && P->d_c1part && !scale_shift && !(dy_colsum && dy_colsum_stride != 0)) {
     // one channel on one side: a streaming kernel with the 27 taps as the GEMM's N axis (conv_c1.hip) instead of padding that side to 32
-    int e = P->c1_in ? mi_launch_c1_wgrad(dy, dy_cs, x, x_cs, dw, dy_colsum, nullptr, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st)
-                     : mi_launch_c1_wgrad(x, x_cs, dy, dy_cs, dw, nullptr, dy_colsum, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cin, 1, st);
+    const int e = P->c1_in ? mi_launch_c1_wgrad(dy, dy_cs, x, x_cs, dw, dy_colsum, nullptr, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st)
+                           : mi_launch_c1_wgrad(x, x_cs, dy, dy_cs, dw, nullptr, dy_colsum, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cin, 1, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
+  // tiled: split partial sums into the plan's slabs, then one reduce into dw (and the column sums)
   WgradArgs w;
-  memset(&w, 0, sizeof(w));
-  w.sx = w.sy = 1; w.cs_chunks = 1;
-  ConvArgs& a = w.c;
-  const bf16* src = (const bf16*)x;
-  int src_cs = x_cs;
-  static const int use_w2 = env_int("MI_WGRAD2", 1);
-  // k3 s2 conv on all axes: the LDS-DMA kernel gathers each pair's class image from x in place (sx = 2) -- no space-to-depth copy
-  bool direct = false;
-  if (P->s2_wg_direct && use_w2 && !scale_shift && (x_cs & 7) == 0 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && P->g_wg.vox == 64) {
-    const int px = (P->g_wg.lds_bytes + 1023) / 1024, py = (P->g_wg.TD * P->g_wg.TH * P->g_wg.TW * 64 + 1023) / 1024;
-    const int64_t dyb = (int64_t)P->N * P->Do * P->Ho * P->Wo * dy_cs * 2, xb = (int64_t)P->N * P->Di * P->Hi * P->Wi * x_cs * 2;
-    direct = px <= 40 && py <= 16 && dyb < (1ll << 32) && xb < (1ll << 32);
-  }
-  if (P->strided && !direct) {
-    int e = mi_space_to_depth(x, x_cs, P->d_xs, P->N, P->Di, P->Hi, P->Wi, P->Cin, P->f[0], P->f[1], P->f[2], st);
-    if (e) return e;
-    src = P->d_xs;
-    src_cs = P->Q * P->Cin;
-  }
-  const bool s2d = P->strided && !direct;
-  a.x = src; a.x_cs = src_cs; a.N = P->N;
-  a.Di = s2d ? P->Dp : P->Di; a.Hi = s2d ? P->Hp : P->Hi; a.Wi = s2d ? P->Wp : P->Wi;
-  a.Cin = s2d ? P->Q * P->Cin : P->Cin;
-  a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
-  a.hdr = direct ? P->d_hdr2 : P->wg.d_hdr; a.taps = P->wg.d_taps; a.nchunks = P->wg.nchunks;
-  if (direct) w.sx = 2;
-  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
-  {
-    int64_t xb = (int64_t)a.N * a.Di * a.Hi * a.Wi * a.x_cs * 2;
-    if (xb >= (1ll << 32)) return MI_ERR_UNSUPPORTED;
-    a.x_bytes = (unsigned)xb;
-  }
-  a.g = P->g_wg;
-  w.dy = (const bf16*)dy; w.dy_cs = dy_cs;
-  w.part = P->d_part; w.pair_off = P->d_pair_off; w.split_stride = P->wg_split_stride;
-  w.ntiles = P->N * a.g.tilesD * a.g.tilesH * a.g.tilesW;
-  w.nsplit = P->wg_nsplit;
-  static const int contig_env = env_int("MI_WGRAD_CONTIG", 1);
-  w.contig = contig_env && (w.ntiles % 8 == 0) && (w.nsplit % 8 == 0) && w.nsplit <= w.ntiles;
-  static const int dbg = mi_diag_knob("MI_WGRAD_DBG");
-  w.dbg = dbg;
-  w.colsum = dy_colsum; w.colsum_stride = dy_colsum_stride;
-  static const int cs_slab = env_int("MI_CS_SLAB", 1);
-  bool cs_pairs_multi_tap = true;  // pairs that own the column sums (first chunk of a cout block) must be tap pairs, not k-split pairs
-  for (int yy = 0; yy < P->wg.ny; ++yy) cs_pairs_multi_tap = cs_pairs_multi_tap && P->wg.hdr[((size_t)yy * P->wg.nchunks) * 4 + 1] > 1;
-  w.cs_part = (cs_slab && dy_colsum && cs_pairs_multi_tap) ? P->d_cspart : nullptr;  if (dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout) return MI_ERR_BAD_ARG;  // 0: one row for the whole batch
-  const int hv = a.g.HD * a.g.HH * a.g.HW;
-  const int np = (hv * 4 + 255) / 256;
-  const int nvox = a.g.TD * a.g.TH * a.g.TW;
-  const int npy = (nvox * 4 + 255) / 256;
-  size_t lds = (size_t)a.g.lds_bytes + (size_t)nvox * a.g.vox;
-  w.npairs = P->wg.ny * P->wg.nchunks;
-  dim3 grid(w.nsplit >= 8 ? w.npairs * ((w.nsplit + 7) / 8) * 8 : w.npairs * w.nsplit), blk(512);
-  if ((a.g.TD * (a.g.TH / 2) * (a.g.TW / 8)) % 2) return MI_ERR_BAD_ARG;  // the k loop is unrolled in pairs
-  if (npy > 4 || np > 16) return MI_ERR_BAD_ARG;  // (256-thread counts; the kernel runs 512 threads: half of each)
-  int max_taps = 0;
-  for (size_t i = 1; i < P->wg.hdr.size(); i += 4) max_taps = P->wg.hdr[i] > max_taps ? P->wg.hdr[i] : max_taps;
-  if (max_taps >= 32) return MI_ERR_UNSUPPORTED;  // wave 7 keeps a spare accumulator for the fused dY column sums
-#define MI_LAUNCH_WG(NPV) MI_LAUNCH_WG_G(NPV, false)
-#define MI_LAUNCH_WG_G(NPV, G3)                                                                                    \
-  do {                                                                                                             \
-    auto kern = k_conv_wgrad<NPV, 2, G3>;                                                                          \
-    static int lds_ok = 0;                                                                                         \
-    if ((int)lds > lds_ok) {                                                                                       \
-      hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-      if (e != hipSuccess) return (int)e;                                                                          \
-      lds_ok = 160 * 1024;                                                                                         \
-    }                                                                                                              \
-    hipLaunchKernelGGL(kern, grid, blk, lds, st, w);                                                               \
-  } while (0)
-  // LDS-DMA kernel (k_conv_wgrad2): whole 8-channel pieces only, no fused prologue
-  {
-    const int px = (a.g.lds_bytes + 1023) / 1024, py = (nvox * 64 + 1023) / 1024;
-    const int64_t dyb = (int64_t)P->N * P->Do * P->Ho * P->Wo * dy_cs * 2;
-    if (use_w2 && !scale_shift && a.g.vox == 64 && (a.x_cs & 7) == 0 && (a.Cin & 7) == 0 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && px <= 40 &&
-        py <= 16 && dyb < (1ll << 32)) {
-      w.dy_bytes = (unsigned)dyb;
-      w.nbuf = (P->KT == 1 && px == 16 && py == 16) ? 4 : 2;  // 1x1: tiles are pure loads -> three tiles in flight per workgroup
-      static const int use_flags = env_int("MI_WGRAD_FLAGS", 1);
-      w.flags = use_flags;
-      const size_t lds2 = (size_t)(w.nbuf * (px + py)) * 1024 + 64;  // + the hand-off counters
-      const bool geo3 = P->full27 && a.g.row == WG3_XROW && a.g.slice == WG3_XSLICE && a.g.TD == 4 && a.g.TH == 8 && a.g.TW == 8;
-      static bool attr3 = false, attrg = false;
-      bool& done = geo3 ? attr3 : attrg;
-      if (!done) {
-        hipError_t e = geo3 ? hipFuncSetAttribute((const void*)k_conv_wgrad2<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)
-                            : hipFuncSetAttribute((const void*)k_conv_wgrad2<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return (int)e;
-        done = true;
-      }
-      static const int use_roll = env_int("MI_WGRAD_ROLL", 1);  // 0: k_conv_wgrad2 for every layer (A/B runs)
-      // (runs of more than two columns lose more to L2 locality -- the workgroups of an XCD are then columns apart -- than the saved
-      // pieces return: 64->64 and 96->32 at 128^3 measured +1 / +2.5 %, 32->32 -6 %, 64->32 -3.5 %, the 64^3 .. 16^3 levels -1.5 .. -3 %)
-      const bool roll = use_roll && geo3 && !direct && w.sx == 1 && w.sy == 1 && w.nbuf == 2 && w.flags && P->wg.hdr[1] == 27 && w.nsplit <= w.ntiles &&
-                        a.g.tilesD >= 2 && (use_roll > 1 || (int64_t)w.ntiles <= 2ll * a.g.tilesD * w.nsplit);
-      if (roll) {
-        static bool attr_r = false;
-        if (!attr_r) {
-          hipError_t e = hipFuncSetAttribute((const void*)k_conv_wgrad3, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-          if (e != hipSuccess) return (int)e;
-          attr_r = true;
-        }
-#ifdef MI_WG3_DIAG_CLK
-        {
-          unsigned long long h0[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, ~0ull, 0};
-          (void)hipDeviceSynchronize();
-          (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg3_clk), h0, sizeof(h0));
-          static unsigned long long z[6][1024];
-          (void)hipMemcpyToSymbol(HIP_SYMBOL(g_wg3_span), z, sizeof(z));
-        }
-#endif
-        hipLaunchKernelGGL(k_conv_wgrad3, grid, dim3(768), (size_t)WR_LDS, st, w);
-#ifdef MI_WG3_DIAG_CLK
-        {
-          unsigned long long h[16];
-          (void)hipDeviceSynchronize();
-          (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg3_clk), sizeof(h));
-          auto us = [&](int a, int b) { return (double)((long long)h[b] - (long long)h[a]) / 100.0; };
-          fprintf(stderr, "[wgrad3 %d->%d ntiles %d nsplit %d] all workgroups: first entry -> last exit %.2f us | workgroup 0 (from the first entry): entry %.2f, "
-                  "compute wave 0: setup %.2f, prologue barrier %.2f, tiles %.2f, final barrier %.2f, stores issued %.2f, stores landed %.2f | loader wave: "
-                  "descriptors %.2f, prologue issue %.2f, landed %.2f us\n", P->Cin, P->Cout, w.ntiles, w.nsplit, us(14, 15), us(14, 0), us(0, 1), us(1, 2), us(2, 3), us(3, 4),
-                  us(4, 5), us(5, 6), us(8, 9), us(9, 10), us(10, 11));
-          static unsigned long long sp[6][1024];
-          (void)hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_wg3_span), sizeof(sp));
-          std::vector<double> ent, dur, ext, lp, pro, bar, iss;
-          for (unsigned b = 0; b < grid.x && b < 1024; ++b)
-            if (sp[1][b]) { bar.push_back((double)(sp[4][b] - h[14]) / 100.0); iss.push_back((double)(sp[5][b] - h[14]) / 100.0); lp.push_back((double)(sp[2][b] - h[14]) / 100.0); pro.push_back((double)(sp[3][b] - h[14]) / 100.0); ent.push_back((double)(sp[0][b] - h[14]) / 100.0); ext.push_back((double)(sp[1][b] - h[14]) / 100.0); dur.push_back((double)(sp[1][b] - sp[0][b]) / 100.0); }
-          std::sort(ent.begin(), ent.end()); std::sort(dur.begin(), dur.end()); std::sort(ext.begin(), ext.end());
-          std::sort(lp.begin(), lp.end()); std::sort(pro.begin(), pro.end()); std::sort(bar.begin(), bar.end()); std::sort(iss.begin(), iss.end());
-          if (!ent.empty()) fprintf(stderr, "    final barrier passed min %.2f median %.2f max %.2f | wave 0 stores issued min %.2f median %.2f max %.2f us\n", bar.front(), bar[bar.size() / 2],
-                                    bar.back(), iss.front(), iss[iss.size() / 2], iss.back());
-          if (!ent.empty()) fprintf(stderr, "    prologue done min %.2f median %.2f max %.2f | tile loop done min %.2f median %.2f max %.2f us\n", pro.front(), pro[pro.size() / 2], pro.back(),
-                                    lp.front(), lp[lp.size() / 2], lp.back());
-          if (!ent.empty()) {
-            auto qt = [](const std::vector<double>& v, double f) { return v[(size_t)(f * (v.size() - 1))]; };
-            fprintf(stderr, "    %zu workgroups: entry 10%% %.2f median %.2f 90%% %.2f max %.2f | exit min %.2f median %.2f max %.2f | lifetime min %.2f median %.2f 90%% %.2f max %.2f us\n",
-                    ent.size(), qt(ent, 0.1), qt(ent, 0.5), qt(ent, 0.9), ent.back(), ext.front(), qt(ext, 0.5), ext.back(), dur.front(), qt(dur, 0.5), qt(dur, 0.9), dur.back());
-          }
-        }
-#endif
-      } else if (geo3) hipLaunchKernelGGL(k_conv_wgrad2<true>, grid, dim3(768), lds2, st, w);
-      else hipLaunchKernelGGL(k_conv_wgrad2<false>, grid, dim3(768), lds2, st, w);
-#ifdef MI_WG2_DIAG_BAR
-      {
-        unsigned long long h[8];
-        (void)hipDeviceSynchronize();
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_wg2_clk), sizeof(h));
-        fprintf(stderr, "[wgrad2] workgroup 0: compute wave 0: %llu cycles over %llu tiles (%llu taps), %llu inside the barrier | loader wave 8: %llu cycles = issue %llu + vmcnt wait %llu + barrier %llu\n",
-                h[4], h[6], h[7], h[5], h[0], h[1], h[2], h[3]);
-      }
-#endif
-      launch_wgrad_reduce(P->d_part, P->wg_split_stride, P->wg_nsplit, P->d_uitems, P->wg_nitems, dw, P->Cout, P->Cin, P->KT, P->d_pair_off,
-                          P->wg.ny * P->wg.nchunks,
-                          CsReduce{w.cs_part ? P->d_cspart : nullptr, P->wg_nsplit, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0}, st);
-      MI_CHECK_LAUNCH();
-      return 0;
-    }
-  }
-  const int np8 = (hv * 4 + 511) / 512;
-  const bool geo3d = P->full27 && a.g.vox == 64 && a.g.row == WG3_XROW && a.g.slice == WG3_XSLICE && a.g.TD == 4 && a.g.TH == 8 &&
-                     a.g.TW == 8 && np8 == 5;
-  if (geo3d) MI_LAUNCH_WG_G(5, true);
-  else if (np8 <= 2) MI_LAUNCH_WG(2);
-  else if (np8 <= 3) MI_LAUNCH_WG(3);
-  else if (np8 <= 5) MI_LAUNCH_WG(5);
-  else MI_LAUNCH_WG(8);
-#undef MI_LAUNCH_WG
-#undef MI_LAUNCH_WG_G
-  launch_wgrad_reduce(P->d_part, P->wg_split_stride, P->wg_nsplit, P->d_uitems, P->wg_nitems, dw, P->Cout, P->Cin, P->KT, P->d_pair_off,
-                      P->wg.ny * P->wg.nchunks, CsReduce{w.cs_part ? P->d_cspart : nullptr, P->wg_nsplit, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0},
-                      st);
+  bool dma, direct;
+  if (int e = wgrad_args(P, x, x_cs, scale_shift, silu, dy, dy_cs, dy_colsum, dy_colsum_stride, w, dma, direct, st)) return e;
+  if (int e = dma ? launch_wgrad_dma(P, w, direct, st) : launch_wgrad_regs(P, w, st)) return e;
+  launch_wgrad_reduce(P->d_part, P->wg_split_stride, P->wg_nsplit, P->d_uitems, P->wg_nitems, dw, P->Cout, P->Cin, P->KT, P->d_pair_off, w.npairs,
+                      CsReduce{w.cs_part ? P->d_cspart : nullptr, P->wg_nsplit, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0}, st);
   MI_CHECK_LAUNCH();
   return 0;
 }
