@@ -257,6 +257,36 @@ int mi_ls_gan_loss(const void* logits, int cs, int64_t nvox, float target, float
 int mi_bn_running_update(const float* mean_rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked, int C, float eps,
                          float momentum, int64_t count, hipStream_t stream);
 
+/* ---- 2-D PatchDiscriminator (the planner's `'2D'` section: configuration.py:966-967 `discriminator_params` with spatial_dims = 2;
+ * train_autoencoder.py:371-397, 416-423, 600): nn.Conv2d(kernel 4, padding 1, stride 2 or 1) on dense NHWC bf16 with kernels of their
+ * own -- no patch matrix.  x [N][H][W][Cin], y / dy [N][Ho][Wo][Cout] (Ho = (H - 2) / stride + 1), w / dw fp32 [Cout][Cin][4][4],
+ * fp32 accumulation.  MI_ERR_BAD_ARG: null pointers, non-positive extents, Ho or Wo < 1, stride outside {1, 2}.
+ * MFMA entry points (the middle layers 64->128, 128->256 at stride 2, 256->512 at stride 1): Cin % 16 == 0 and Cout % 32 == 0, otherwise
+ * MI_ERR_UNSUPPORTED.  The gathered NT GEMM of csrc/disc2d.hip; index arithmetic in csrc/conv2d_k4_index.h. */
+/* w -> w_fwd [Cout][16 Cin] bf16, K order (th, tw, ci), and (may be NULL) w_dgrad, 16 Cin Cout bf16: [Cin][(th, tw, co)] at stride 1,
+ * [4 parity classes][Cin][(2 x 2 taps, co)] at stride 2 */
+int mi_conv2d_k4_pack(const float* w, void* w_fwd, void* w_dgrad, int Cin, int Cout, int stride, hipStream_t stream);
+int mi_conv2d_k4_fwd(const void* x, const void* w_fwd, void* y, int N, int H, int W, int Cin, int Cout, int stride, hipStream_t stream);
+/* dx [N][H][W][Cin], every element written (a gather over dy: no atomics) */
+int mi_conv2d_k4_dgrad(const void* dy, const void* w_dgrad, void* dx, int N, int H, int W, int Cin, int Cout, int stride,
+                       hipStream_t stream);
+/* dw += the weight gradient, bit-identical from run to run: pixel ranges into fp32 slabs, folded in a fixed order.  workspace: fp32,
+ * splits * 16 * Cin * Cout elements with splits from the query below (0: arguments out of range) */
+int mi_conv2d_k4_wgrad_splits(int N, int H, int W, int Cin, int Cout, int stride);
+int mi_conv2d_k4_wgrad(const void* x, const void* dy, float* dw, float* workspace, int N, int H, int W, int Cin, int Cout, int stride,
+                       hipStream_t stream);
+/* Edge layers (initial_conv: the image's Cin < 8 with bias; final_conv: Cout = 1 with bias): VALU direct kernels, any channel counts;
+ * weights are read as fp32 and rounded to bf16 like the packs; bias fp32 [Cout] or NULL.  The logits are stored unpadded. */
+int mi_conv2d_k4_edge_fwd(const void* x, const float* w, const float* bias, void* y, int N, int H, int W, int Cin, int Cout, int stride,
+                          hipStream_t stream);
+int mi_conv2d_k4_edge_dgrad(const void* dy, const float* w, void* dx, int N, int H, int W, int Cin, int Cout, int stride,
+                            hipStream_t stream);
+/* dw += weight gradient, dbias (may be NULL) += column sums of dy, same fixed-order fold; workspace: fp32,
+ * splits * (16 * Cin * Cout + Cout) elements */
+int mi_conv2d_k4_edge_wgrad_splits(int N, int H, int W, int Cin, int Cout, int stride);
+int mi_conv2d_k4_edge_wgrad(const void* x, const void* dy, float* dw, float* dbias, float* workspace, int N, int H, int W, int Cin,
+                            int Cout, int stride, hipStream_t stream);
+
 /* ---- LPIPS-VGG perceptual loss of the generator step (train_autoencoder.py:416 `perceptual_loss(recon, images) * perc_weight`, :601
  * `PerceptualLoss(**perceptual_params)`; third-party `generative` / `lpips` classes: PARITY UNPINNED).  The VGG16 3x3 convs run on 2-D
  * conv plans (kernel (1,3,3), padding (0,1,1)) with forward and data gradient only; slices are [S][A][B][C] bf16 (the plans' D = 1).

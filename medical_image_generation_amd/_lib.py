@@ -86,6 +86,15 @@ _SIGS = {
     "mi_col2im3d": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
     "mi_disc_pack_weights": [_p, _p, _p, _i, _i, _i, _i, _p],
     "mi_disc_wgrad_unpack": [_p, _p, _i, _i, _i, _p],
+    "mi_conv2d_k4_pack": [_p, _p, _p, _i, _i, _i, _p],
+    "mi_conv2d_k4_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "mi_conv2d_k4_dgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "mi_conv2d_k4_wgrad_splits": [_i, _i, _i, _i, _i, _i],
+    "mi_conv2d_k4_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "mi_conv2d_k4_edge_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "mi_conv2d_k4_edge_dgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
+    "mi_conv2d_k4_edge_wgrad_splits": [_i, _i, _i, _i, _i, _i],
+    "mi_conv2d_k4_edge_wgrad": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
     "mi_perc_gather": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p],
     "mi_perc_scatter_add": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p],
     "mi_pad_cin_f32": [_p, _p, _i, _i, _i, _i, _p],
@@ -119,13 +128,14 @@ _SIGS = {
     "mi_kl_eval": [_p, _p, _p, _i, _i, _l, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l}
-_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks"}
+_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
+            "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits"}
 
 _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 
 def exported_symbols() -> list[str]:

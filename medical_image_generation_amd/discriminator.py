@@ -8,9 +8,10 @@ constructor surface, `state_dict()` names (`initial_conv.conv.*`, `<l>.conv.weig
 (conv weights N(0, 0.02), BatchNorm weights N(1, 0.02), biases 0) and forward (the list of every layer's output) as restated in
 oracle/disc.py -- PARITY UNPINNED against the original.
 
-Kernels: csrc/disc.hip -- the k4 convs (stride 2 / 1, padding 1) run as patch matrix + the library's bf16 NT GEMM, BatchNorm in
+Kernels: csrc/disc.hip -- the 3-D k4 convs (stride 2 / 1, padding 1) run as patch matrix + the library's bf16 NT GEMM, BatchNorm in
 training mode as GroupNorm with one channel per group on the [1, N*V, C] view (activation code 2 = LeakyReLU(0.2)), the loss as one
-small kernel.  3-D only (the 2-D planner configs keep upstream's torch discriminator through AETrainer(extra_loss=...)).
+small kernel.  csrc/disc2d.hip -- the 2-D k4 convs (the planner's `'2D'` section) have kernels of their own: a gathered NT GEMM for
+the middle layers, VALU direct kernels for the image and logits layers, no patch matrix (`conv2d_k4`).
 """
 from __future__ import annotations
 
@@ -19,7 +20,7 @@ from torch import nn
 
 from . import engine as E
 from . import hipops as ops
-from ._lib import call, ptr
+from ._lib import call, call_raw, ptr
 from .unet import HipModule, ParamSpec, _NetFn
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -79,6 +80,66 @@ def conv_gemm(ctx: E.Ctx, x, name, k, s, p, bias: bool, need_dx=True, param_grad
     return y
 
 
+def _mfma_layer(cin, cout):
+    """The channel counts the gathered MFMA GEMM of csrc/disc2d.hip covers (the middle layers); everything else is an edge layer."""
+    return cin % 16 == 0 and cout % 32 == 0
+
+
+def conv2d_k4(ctx: E.Ctx, x, name, stride, bias: bool, need_dx=True, param_grads=True):
+    """nn.Conv2d(kernel 4, padding 1, stride 2 / 1) on [N, 1, H, W, Cin] bf16 (weight `name.weight` [Cout, Cin, 4, 4]) -> y [N, 1, Ho, Wo, Cout],
+    dense and unpadded.  Cin % 16 == 0 and Cout % 32 == 0: the gathered MFMA GEMMs (weights packed once per call); otherwise (the image
+    layer, the logits layer) the VALU direct kernels.  No patch matrix in either."""
+    n, d, h, w, cin = x.shape
+    assert d == 1
+    wt = ctx.p(name + ".weight")
+    cout = wt.shape[0]
+    ho, wo = ((v - 2) // stride + 1 for v in (h, w))
+    dev = x.device
+    dims = (n, h, w, cin, cout, stride)
+    mfma = _mfma_layer(cin, cout) and not bias  # (the MFMA GEMM has no bias epilogue: the reference's middle layers have none)
+    xd = ops.dense(x)
+    y = torch.empty((n, 1, ho, wo, cout), dtype=BF16, device=dev)
+    wd = None
+    if mfma:
+        wf = torch.empty((cout, 16 * cin), dtype=BF16, device=dev)
+        if need_dx and ctx.tape is not None:
+            wd = torch.empty(16 * cin * cout, dtype=BF16, device=dev)
+        call("mi_conv2d_k4_pack", ptr(wt), ptr(wf), ptr(wd), cin, cout, stride)
+        call("mi_conv2d_k4_fwd", ptr(xd), ptr(wf), ptr(y), *dims)
+    else:
+        call("mi_conv2d_k4_edge_fwd", ptr(xd), ptr(wt), ptr(ctx.p(name + ".bias")) if bias else None, ptr(y), *dims)
+    ctx.count(2 * n * ho * wo * cout * 16 * cin, dgrad=need_dx, wgrad=param_grads)
+    if ctx.tape is not None:
+        tape = ctx.tape
+
+        def bwd():
+            dy = tape.take(y)
+            if dy is None:
+                return
+            dy = ops.dense(dy)
+            if param_grads:
+                splits = call_raw("mi_conv2d_k4_wgrad_splits" if mfma else "mi_conv2d_k4_edge_wgrad_splits", *dims)
+                if splits <= 0:
+                    raise ValueError(f"conv2d_k4 {name}: no weight-gradient plan for {dims}")
+                if mfma:
+                    ws = torch.empty(splits * 16 * cin * cout, dtype=F32, device=dev)
+                    call("mi_conv2d_k4_wgrad", ptr(xd), ptr(dy), ptr(ctx.g(name + ".weight")), ptr(ws), *dims)
+                else:
+                    ws = torch.empty(splits * (16 * cin * cout + cout), dtype=F32, device=dev)
+                    call("mi_conv2d_k4_edge_wgrad", ptr(xd), ptr(dy), ptr(ctx.g(name + ".weight")), ptr(ctx.g(name + ".bias")) if bias else None,
+                         ptr(ws), *dims)
+            if need_dx:
+                dx = torch.empty((n, 1, h, w, cin), dtype=BF16, device=dev)
+                if mfma:
+                    call("mi_conv2d_k4_dgrad", ptr(dy), ptr(wd), ptr(dx), *dims)
+                else:
+                    call("mi_conv2d_k4_edge_dgrad", ptr(dy), ptr(wt), ptr(dx), *dims)
+                tape.put(x, dx)
+
+        tape.record(bwd)
+    return y
+
+
 def leaky_relu(ctx: E.Ctx, x, slope=0.2):
     y = torch.empty_like(x)
     call("mi_leaky_relu_fwd", ptr(x), ptr(y), x.numel(), float(slope))
@@ -127,14 +188,27 @@ def batchnorm_leaky(ctx: E.Ctx, x, name, buffers, eps=1e-5, momentum=0.1, param_
 class PatchDiscriminator(HipModule):
     """`generative.networks.nets.PatchDiscriminator(spatial_dims, num_channels, in_channels, out_channels=1, num_layers_d=3, kernel_size=4,
     activation=LeakyReLU(0.2), norm="BATCH", bias=False, padding=1, dropout=0.0, last_conv_kernel_size=None)`; forward returns the list
-    of the outputs of initial_conv, layers 0 .. num_layers_d-1 and final_conv (the reference takes `[-1]`, the patch logits)."""
+    of the outputs of initial_conv, layers 0 .. num_layers_d-1 and final_conv (the reference takes `[-1]`, the patch logits).
+
+    spatial_dims=3: any channel counts, any kernel_size (patch matrix + GEMM).
+    spatial_dims=2 (native kernels, csrc/disc2d.hip) covers `num_channels % 16 == 0` (the planner's is 64), `kernel_size == 4`,
+    `padding == 1` and `last_conv_kernel_size in (None, 4)`; any other 2-D configuration raises NotImplementedError naming the
+    constraint -- narrow nets are not routed onto the edge kernels.  The other restrictions are those of 3-D.  Inputs are NCHW fp32,
+    the outputs NCHW; `_run` takes [N, 1, H, W, C] channels-last and returns the logits unpadded ([N, 1, h, w, 1])."""
 
     def __init__(self, spatial_dims: int, num_channels: int, in_channels: int, out_channels: int = 1, num_layers_d: int = 3, kernel_size: int = 4,
                  activation=("LEAKYRELU", {"negative_slope": 0.2}), norm="BATCH", bias: bool = False, padding: int = 1, dropout: float = 0.0,
                  last_conv_kernel_size: int | None = None) -> None:
         super().__init__()
-        if spatial_dims != 3:
-            raise NotImplementedError("the HIP PatchDiscriminator is 3-D (2-D configs: upstream's torch module through AETrainer(extra_loss=))")
+        if spatial_dims not in (2, 3):
+            raise NotImplementedError("spatial_dims must be 2 or 3")
+        if spatial_dims == 2:
+            if num_channels % 16:
+                raise NotImplementedError(f"the 2-D HIP PatchDiscriminator needs num_channels % 16 == 0 (got {num_channels}): its middle layers "
+                                          "run on the MFMA k4 conv, which takes Cin % 16 == 0 and Cout % 32 == 0")
+            if kernel_size != 4 or padding != 1 or last_conv_kernel_size not in (None, 4):
+                raise NotImplementedError("the 2-D HIP PatchDiscriminator covers kernel_size == 4, padding == 1 and last_conv_kernel_size in "
+                                          f"(None, 4) (got {kernel_size}, {padding}, {last_conv_kernel_size})")
         if str(norm).upper() != "BATCH" or dropout != 0.0 or bias or out_channels != 1:
             raise NotImplementedError("only the configuration the reference builds: norm='BATCH', bias=False, dropout=0, out_channels=1")
         act_name = activation[0] if isinstance(activation, (tuple, list)) else activation
@@ -145,14 +219,14 @@ class PatchDiscriminator(HipModule):
         self.num_channels, self.num_layers_d = num_channels, num_layers_d
         self.kernel_size, self.padding = kernel_size, padding
         self.last_k = kernel_size if last_conv_kernel_size is None else last_conv_kernel_size
-        spec = ParamSpec(self, 3)
+        spec = ParamSpec(self, spatial_dims)
 
         def conv(name, cin, cout, k, with_bias):
-            w = torch.empty(cout, cin, k, k, k)
-            nn.init.normal_(w, 0.0, 0.02)  # initialise_weights: Conv3d weights N(0, 0.02); the bias keeps nn.Conv3d's default
+            w = torch.empty(cout, cin, *([k] * spatial_dims))
+            nn.init.normal_(w, 0.0, 0.02)  # initialise_weights: Conv{2,3}d weights N(0, 0.02); the bias keeps nn.Conv{2,3}d's default
             spec._add(name + ".weight", w)
             if with_bias:
-                bound = 1 / (cin * k ** 3) ** 0.5
+                bound = 1 / (cin * k ** spatial_dims) ** 0.5
                 spec._add(name + ".bias", torch.empty(cout).uniform_(-bound, bound))
 
         conv("initial_conv.conv", in_channels, num_channels, kernel_size, True)
@@ -176,7 +250,10 @@ class PatchDiscriminator(HipModule):
         return mod.running_mean, mod.running_var, mod.num_batches_tracked
 
     def _run(self, c: E.Ctx, x_cl, need_dx=True, param_grads=True):
-        """-> [outputs]; the last one is the logits tensor [N, d, h, w, 8] whose channel 0 (.. out_channels) is real, the rest padding."""
+        """-> [outputs]; the last one is the logits tensor: 3-D [N, d, h, w, 8] whose channel 0 (.. out_channels) is real, the rest
+        padding; 2-D [N, 1, h, w, 1]."""
+        if self.spatial_dims == 2:
+            return self._run2d(c, x_cl, need_dx, param_grads)
         k, p = self.kernel_size, self.padding
         outs = []
         h = conv_gemm(c, x_cl, "initial_conv.conv", k, 2, p, True, need_dx=need_dx, param_grads=param_grads)
@@ -189,7 +266,21 @@ class PatchDiscriminator(HipModule):
         outs.append(conv_gemm(c, h, "final_conv.conv", self.last_k, 1, (self.last_k - 1) // 2, True, param_grads=param_grads))
         return outs
 
+    def _run2d(self, c: E.Ctx, x_cl, need_dx, param_grads):
+        outs = []
+        h = conv2d_k4(c, x_cl, "initial_conv.conv", 2, True, need_dx=need_dx, param_grads=param_grads)
+        h = leaky_relu(c, h, 0.2)
+        outs.append(h)
+        for name, _, _, stride in self._layers:
+            h = conv2d_k4(c, h, name + ".conv", stride, False, param_grads=param_grads)
+            h = batchnorm_leaky(c, h, name + ".adn.N", self._buffers_of(name), param_grads=param_grads)
+            outs.append(h)
+        outs.append(conv2d_k4(c, h, "final_conv.conv", 1, True, param_grads=param_grads))
+        return outs
+
     def forward(self, x: torch.Tensor):
+        if x.dim() != self.spatial_dims + 2:
+            raise ValueError(f"expected a {self.spatial_dims + 2}-D input, got {tuple(x.shape)}")
         if x.shape[1] != self.in_channels:
             raise ValueError(f"expected {self.in_channels} input channels, got {x.shape[1]}")
         if not x.is_cuda:
