@@ -349,6 +349,16 @@ int mi_ddpm_step(float* x, const void* eps, const float* noise, const float* coe
                  int C, int64_t V, int clip, hipStream_t stream);
 /* (x_cl_cs >= C: voxel pitch of x_cl in elements -- with mode="concat" sampling the model input holds the condition channels behind
  * the C sample channels and only the sample channels are rewritten per step) */
+/* one step of DDIMScheduler.step / reversed_step (third-party `generative`; Song et al. 2021 as upstream implements it, restated in
+ * tests/ddim_ref.py: PARITY UNPINNED -- the reference holds no vectors for it), the few-step scheduler that passes to the same
+ * `inferer.sample(..., scheduler=...)` call (train_ldm.py:351-364).  Layouts as above: x fp32 NCDHW updated in place, model_out NDHWC
+ * bf16, noise fp32 NCDHW (read only where r4 != 0), x_cl optional NDHWC bf16 with voxel pitch x_cl_cs >= C (channels behind the first
+ * C are not touched).  rows: [S][5] fp32 on the device, built by the host per direction, stride and eta =
+ * sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma;  row_index: device pointer to the row of this step.
+ *   epsilon: x0 = (x - r1 m) / r0, e = m;   v-prediction: x0 = r0 x - r1 m, e = r0 m + r1 x;   x_next = r2 clip(x0) + r3 e + r4 z
+ * flags: bit 0 = clip_sample, bit 1 = v-prediction (as the clip argument above) */
+int mi_ddim_step(float* x, const void* model_out, const float* noise, const float* rows, const int64_t* row_index, void* x_cl,
+                 int x_cl_cs, int N, int C, int64_t V, int flags, hipStream_t stream);
 /* loss = mean((pred - target)^2); dpred = grad_scale * 2 (pred - target) / numel (grad_scale 1.0 = F.mse_loss(...).backward());
  * pred NDHWC bf16 and target NCDHW fp32 must BOTH have C channels (the caller checks: a 9-channel target read with C = 8 lines up
  * for the first image only) */

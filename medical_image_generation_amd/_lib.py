@@ -111,6 +111,7 @@ _SIGS = {
     "mi_bn_running_update": [_p, _p, _p, _p, _i, _f, _f, _l, _p],
     "mi_qsample": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p],
     "mi_ddpm_step": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
+    "mi_ddim_step": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
     "mi_mse_fwd_bwd": [_p, _p, _p, _p, _i, _i, _l, _f, _p],
     "mi_l1_fwd_bwd": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
     "mi_reparam_kl_fwd": [_p, _p, _p, _p, _p, _i, _i, _l, _f, _p],
@@ -135,7 +136,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 13
+ABI_VERSION = 14
 
 
 def exported_symbols() -> list[str]:

@@ -269,6 +269,40 @@ __global__ void k_ddpm_step(float* __restrict__ x, const bf16* __restrict__ eps,
     }
   }
 }
+// One step of DDIMScheduler.step / reversed_step (third-party `generative`; closed form of Song et al. 2021 as upstream implements it,
+// restated in tests/ddim_ref.py: PARITY UNPINNED; the few-step path of the sample loop at train_ldm.py:351-364).  The direction
+// (denoising or inversion), the stride and eta are all in the row, which the host builds: rows [S][5] = sqrt(a_t), sqrt(1 - a_t),
+// sqrt(a_prev), sqrt(1 - a_prev - sigma^2), sigma;  row_index: device scalar, the row of this step.
+//   epsilon:      x0 = (x - r1 m) / r0,   e = m            v-prediction (flags & 2):  x0 = r0 x - r1 m,   e = r0 m + r1 x
+//   x0 clamped to +-1 when flags & 1 (e is NOT recomputed from the clamped x0);  x_next = r2 x0 + r3 e + r4 z
+// Layouts as k_ddpm_step: x fp32 NCDHW in place, m NDHWC bf16, z fp32 NCDHW (read only where r4 != 0), x_cl the next model input.
+__global__ void k_ddim_step(float* __restrict__ x, const bf16* __restrict__ mo_cl, const float* __restrict__ z, const float* __restrict__ rows,
+                            const int64_t* __restrict__ row_index, bf16* __restrict__ x_cl, int x_cl_cs, int C, int64_t V, int64_t total,
+                            int flags) {
+  const float* r = rows + row_index[0] * 5;
+  const float r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3], r4 = r[4];
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t n = i / V, v = i - n * V;
+    for (int c = 0; c < C; ++c) {
+      const int64_t s = (n * C + c) * V + v;
+      const float xt = x[s];
+      const float mo = bf2f(mo_cl[i * C + c]);
+      float x0, e;
+      if (flags & 2) {
+        x0 = r0 * xt - r1 * mo;
+        e = r0 * mo + r1 * xt;
+      } else {
+        x0 = (xt - r1 * mo) / r0;
+        e = mo;
+      }
+      if (flags & 1) x0 = fminf(fmaxf(x0, -1.f), 1.f);
+      float xn = r2 * x0 + r3 * e;
+      if (r4 != 0.f) xn += r4 * z[s];
+      x[s] = xn;
+      if (x_cl) x_cl[i * x_cl_cs + c] = f2bf(xn);
+    }
+  }
+}
 // loss = mean((pred - target)^2) over all elements; dpred = 2 (pred - target) / numel * loss_scale.
 // pred NDHWC bf16, target NCDHW fp32, dpred NDHWC bf16.  loss accumulated with one atomic per block into *loss_sum.
 __global__ void k_mse(const bf16* __restrict__ pred, const float* __restrict__ target, bf16* __restrict__ dpred,
@@ -601,6 +635,15 @@ int mi_ddpm_step(float* x, const void* eps, const float* noise, const float* coe
   if (total <= 0 || C <= 0 || !x || !eps || !noise || !coef || !t || (x_cl && x_cl_cs < C)) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_ddpm_step, dim3(grid_for(total)), dim3(kThreads), 0, st, x, (const bf16*)eps, noise, coef, t, (bf16*)x_cl, x_cl_cs, C, V,
                      total, clip);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+int mi_ddim_step(float* x, const void* model_out, const float* noise, const float* rows, const int64_t* row_index, void* x_cl, int x_cl_cs,
+                 int N, int C, int64_t V, int flags, hipStream_t st) {
+  int64_t total = (int64_t)N * V;
+  if (N <= 0 || V <= 0 || C <= 0 || !x || !model_out || !noise || !rows || !row_index || (x_cl && x_cl_cs < C)) return MI_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_ddim_step, dim3(grid_for(total)), dim3(kThreads), 0, st, x, (const bf16*)model_out, noise, rows, row_index, (bf16*)x_cl,
+                     x_cl_cs, C, V, total, flags);
   MI_CHECK_LAUNCH();
   return 0;
 }

@@ -10,6 +10,10 @@ tests pin the kernel against that restatement.
 One denoising step = UNet forward (no tape) + ONE fused update kernel (`mi_ddpm_step`: predicted x0, clip, posterior mean, noise;
 it also writes the next step's channels-last bf16 model input), captured once as a hipGraph and replayed per timestep -- the
 timestep is a device scalar the embedding and update kernels read, so all 1000 steps share one graph.
+
+Few-step sampling and image-to-noise inversion go through `DDIMScheduler` (third-party `generative` as well, Song et al. 2021 as
+upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED): the same loop with `mi_ddim_step` as the update kernel,
+which reads row i of a per-run table of step constants, so step count, eta and direction change without a new capture.
 """
 from __future__ import annotations
 
@@ -90,6 +94,109 @@ class DDPMScheduler:
         return prev, x0
 
 
+class DDIMScheduler:
+    """`generative.networks.schedulers.DDIMScheduler`: the few-step sampler that passes to the same `inferer.sample(..., scheduler=...)`
+    call (train_ldm.py:351-364), and `reversed_step`, image-to-noise inversion.  The upstream source is absent; the arithmetic is the
+    closed form of Song et al. 2021 as upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED -- the reference holds
+    no vectors for it.
+
+    Unlike a strided DDPMScheduler, whose coefficients take alphas_cumprod[t-1] as the previous level whatever the stride, the
+    previous level here is alphas_cumprod[t - T // n]: this is the scheduler to use with n < T steps.
+
+    Per-step constants are rows [r0..r4] = sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma, built in fp64 with
+    every radicand clamped at 0 and kept as fp32; the update for sample x, model output m, noise z:
+        epsilon: x0 = (x - r1 m) / r0, e = m;    v_prediction: x0 = r0 x - r1 m, e = r0 m + r1 x
+        x_next = r2 clip(x0) + r3 e + r4 z       (e is not recomputed from the clipped x0)"""
+
+    def __init__(self, num_train_timesteps=1000, schedule="linear_beta", clip_sample=True, set_alpha_to_one=True, steps_offset=0,
+                 prediction_type="epsilon", beta_start=1e-4, beta_end=2e-2):
+        if prediction_type not in ("epsilon", "v_prediction"):
+            raise ValueError(f"unknown prediction_type {prediction_type}")
+        self.betas = betas(schedule, num_train_timesteps, beta_start, beta_end)
+        self.num_train_timesteps, self.prediction_type, self.clip_sample = num_train_timesteps, prediction_type, clip_sample
+        self.steps_offset = steps_offset
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]  # the level "before" t = 0
+        self.first_alpha_cumprod = torch.tensor(0.0)  # the level "after" t = T - 1 (inversion): pure noise
+        self._table = None
+        # every training timestep, descending; steps_offset shifts the strided subsets of set_timesteps only
+        self.num_inference_steps = num_train_timesteps
+        self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1, dtype=torch.int64)
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        if num_inference_steps > self.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`: "
+                             f"{self.num_train_timesteps}")
+        ratio = self.num_train_timesteps // num_inference_steps
+        timesteps = (torch.arange(0, num_inference_steps) * ratio).flip(0).to(torch.int64) + self.steps_offset
+        if int(timesteps[0]) >= self.num_train_timesteps:
+            raise ValueError(f"`steps_offset`: {self.steps_offset} moves the largest of {num_inference_steps} timesteps to "
+                             f"{int(timesteps[0])}, past `self.num_train_timesteps`: {self.num_train_timesteps}")
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = timesteps if device is None else timesteps.to(device)
+
+    def _rows(self, t, eta=0.0, reverse=False):
+        """fp32 [len(t), 5]: the constants of the steps that leave the timesteps t (int64), towards t - ratio (denoising) or
+        t + ratio (reverse=True), computed in fp64."""
+        acp, ratio = self.alphas_cumprod.double(), self.num_train_timesteps // self.num_inference_steps
+        t = t.cpu()
+        a = acp[t]
+        if reverse:
+            p = t + ratio
+            ap = torch.where(p < self.num_train_timesteps, acp[p.clamp(max=self.num_train_timesteps - 1)], self.first_alpha_cumprod.double())
+            sigma = torch.zeros_like(a)
+        else:
+            p = t - ratio
+            ap = torch.where(p >= 0, acp[p.clamp(min=0)], self.final_alpha_cumprod.double())
+            sigma = eta * ((1 - ap) / (1 - a) * (1 - a / ap)).clamp(min=0).sqrt()
+        return torch.stack([a.sqrt(), (1 - a).clamp(min=0).sqrt(), ap.sqrt(), (1 - ap - sigma ** 2).clamp(min=0).sqrt(), sigma], dim=1).float()
+
+    def rows(self, eta=0.0, reverse=False):
+        """One row per step in the order the loop takes them: self.timesteps, or ascending for reverse=True (inversion)."""
+        return self._rows(self.timesteps.flip(0) if reverse else self.timesteps, eta, reverse).contiguous()
+
+    def coefficients(self, device):
+        """The device row table the fused loop reads, [num_train_timesteps, 5]: one allocation per device at full capacity, so a
+        captured graph that points at it stays valid over set_timesteps, eta and direction -- the loop refills it before it steps."""
+        if self._table is None or self._table.device != torch.device(device):
+            self._table = torch.zeros(self.num_train_timesteps, 5, dtype=F32, device=device)
+        return self._table
+
+    def add_noise(self, original_samples, noise, timesteps):
+        a = self.alphas_cumprod.to(original_samples.device)[timesteps]
+        shape = (-1,) + (1,) * (original_samples.ndim - 1)
+        return (a ** 0.5).reshape(shape) * original_samples + ((1 - a) ** 0.5).reshape(shape) * noise
+
+    def get_velocity(self, sample, noise, timesteps):
+        a = self.alphas_cumprod.to(sample.device)[timesteps]
+        shape = (-1,) + (1,) * (sample.ndim - 1)
+        return (a ** 0.5).reshape(shape) * noise - ((1 - a) ** 0.5).reshape(shape) * sample
+
+    def _update(self, r, model_output, sample):
+        if self.prediction_type == "v_prediction":
+            x0, e = r[0] * sample - r[1] * model_output, r[0] * model_output + r[1] * sample
+        else:
+            x0, e = (sample - r[1] * model_output) / r[0], model_output
+        if self.clip_sample:
+            x0 = x0.clamp(-1, 1)
+        return r[2] * x0 + r[3] * e, x0
+
+    def step(self, model_output, timestep, sample, eta=0.0, generator=None):
+        """(prev_sample, pred_original_sample) for fp32 NC[D]HW tensors -- the upstream signature; plain torch on any device (the
+        fused loop of the inferers below does not go through the tensor-level methods)."""
+        r = self._rows(torch.tensor([int(timestep)]), eta)[0].to(sample.device)
+        prev, x0 = self._update(r, model_output, sample)
+        if eta > 0:
+            prev = prev + r[4] * torch.randn(sample.shape, generator=generator, device=sample.device, dtype=sample.dtype)
+        return prev, x0
+
+    def reversed_step(self, model_output, timestep, sample):
+        """(post_sample, pred_original_sample): one deterministic step towards noise, from `timestep` to `timestep + ratio`."""
+        r = self._rows(torch.tensor([int(timestep)]), reverse=True)[0].to(sample.device)
+        return self._update(r, model_output, sample)
+
+
 class _Loop:
     """One captured denoising step, replayed over scheduler.timesteps."""
 
@@ -109,8 +216,9 @@ class _Loop:
         self.x_cl = torch.empty((n,) + dims + (c + self.cc,), dtype=torch.bfloat16, device=device)  # ... as the model reads it (+ condition)
         self.ctx = None if context_shape is None else torch.empty((n * context_shape[0], context_shape[1]), dtype=torch.bfloat16, device=device)
         self.z = torch.empty(shape, dtype=F32, device=device)
-        self.t = torch.zeros(1, dtype=torch.int64, device=device)
-        self.tn = torch.zeros(n, dtype=torch.int64, device=device)
+        self.ddim = isinstance(scheduler, DDIMScheduler)
+        self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its table with: t (DDPM), step i (DDIM)
+        self.tn = torch.zeros(n, dtype=torch.int64, device=device)  # the timestep the model reads
         self.coef = scheduler.coefficients(device)
         self.arena = model.arena(device)
         self.graph = None
@@ -120,15 +228,16 @@ class _Loop:
     def _step(self):
         ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
         eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, context=self.ctx)
-        call("mi_ddpm_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.x_cl), self.c + self.cc, self.n, self.c,
-             self.v, int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0))
+        call("mi_ddim_step" if self.ddim else "mi_ddpm_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.x_cl),
+             self.c + self.cc, self.n, self.c, self.v, int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0))
 
     def _load(self, x):
         """x (fp32 NC[D]HW) -> the sample channels of the model input (the condition channels behind them stay)."""
         self.x.copy_(x)
         self.x_cl[..., :self.c].copy_(ops.to_channels_last(self.x))
 
-    def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None):
+    def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None, eta=0.0, reverse=False):
+        """eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps."""
         if self.m._arena is not self.arena:  # the module moved (.to / .cuda): plans and graph point at the old buffers -> start over
             self.arena, self.graph, self.keys, self._pinned = self.m.arena(self.x.device), None, (), None
         if self.cc:  # mode="concat": model_input = cat([image, conditioning], dim=1) at every step; written once, the steps rewrite `image`
@@ -137,6 +246,11 @@ class _Loop:
             self.ctx.copy_(ops.cast_bf16(conditioning.contiguous().reshape(-1, conditioning.shape[2])))
         self._load(input_noise)
         steps = [int(t) for t in self.sch.timesteps]
+        if self.ddim:  # the rows of THIS run, written into the table the (possibly already captured) step reads, before any step runs
+            if reverse:
+                steps.reverse()
+            self.coef[:len(steps)].copy_(self.sch.rows(eta, reverse))
+            self.t.zero_()
         keep = self.x.clone()
         if not self.m._plans or len(self.keys) != len(self.m._plans):
             self.keys = ()
@@ -157,11 +271,13 @@ class _Loop:
             self._pinned = (dict(self.m._plans), dict(ops._ws_cache), self.arena)  # keep what the graph points at alive
         self._load(keep)
         for i, t in enumerate(steps):
-            self.t.fill_(t)
+            self.t.fill_(i if self.ddim else t)
             self.tn.fill_(t)
-            if noises is not None:
+            if self.ddim and (reverse or eta == 0):
+                pass  # deterministic rows (sigma = 0): the kernel does not read z
+            elif noises is not None:
                 self.z.copy_(noises[i])
-            elif t > 0:
+            elif self.ddim or t > 0:
                 self.z.normal_(generator=generator)
             if self.graph is not None:
                 self.graph.replay()
@@ -201,35 +317,40 @@ class DiffusionInferer:
             noisy, condition = torch.cat([noisy, condition.to(noisy.dtype)], dim=1), None
         return diffusion_model(x=noisy, timesteps=timesteps, context=condition)
 
-    @torch.no_grad()
-    def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
-               mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True):
-        """conditioning with mode="concat": fp32 NC'[D]HW, model_input = cat([image, conditioning], dim=1) at every step; with
-        mode="crossattn": fp32 [N, tokens, cross_attention_dim], the model's `context` (train_ldm.py:349-365 passes neither).
-        noises: optional sequence with the z of every step (tests pin them); generator: torch generator for the per-step noise."""
+    def _conditioning(self, x, diffusion_model, conditioning, mode):
+        """The checks of a sample / invert call -> (conditioning as fp32 on x's device, concat channels, cross-attention context shape)."""
         self._check_mode(mode)
-        if not input_noise.is_cuda:
+        if not x.is_cuda:
             raise RuntimeError("medical_image_generation_amd runs on MI355X only: move the inputs to 'cuda'")
         cc, ctx_shape = 0, None
         if conditioning is not None:
-            conditioning = conditioning.to(device=input_noise.device, dtype=F32).contiguous()
+            conditioning = conditioning.to(device=x.device, dtype=F32).contiguous()
             if mode == "concat":
-                if conditioning.dim() != input_noise.dim() or conditioning.shape[0] != input_noise.shape[0] or \
-                        conditioning.shape[2:] != input_noise.shape[2:]:
+                if conditioning.dim() != x.dim() or conditioning.shape[0] != x.shape[0] or conditioning.shape[2:] != x.shape[2:]:
                     raise ValueError("mode='concat': conditioning must have the sample's batch and spatial shape")
                 cc = conditioning.shape[1]
             else:
                 if not getattr(diffusion_model, "with_conditioning", False):
                     raise ValueError("model should have with_conditioning = True if context is provided")
-                if conditioning.dim() != 3 or conditioning.shape[0] != input_noise.shape[0] or \
+                if conditioning.dim() != 3 or conditioning.shape[0] != x.shape[0] or \
                         conditioning.shape[2] != diffusion_model.cross_attention_dim:
                     raise ValueError(f"mode='crossattn': conditioning must be [batch, tokens, {diffusion_model.cross_attention_dim}]")
                 ctx_shape = (conditioning.shape[1], conditioning.shape[2])
         elif getattr(diffusion_model, "with_conditioning", False):
             raise ValueError("the model was built with_conditioning=True: pass conditioning=[batch, tokens, cross_attention_dim]")
-        if input_noise.shape[1] + cc != diffusion_model.in_channels:
-            raise ValueError(f"Input number of channels ({input_noise.shape[1] + cc}) is not equal to expected number of channels "
+        if x.shape[1] + cc != diffusion_model.in_channels:
+            raise ValueError(f"Input number of channels ({x.shape[1] + cc}) is not equal to expected number of channels "
                              f"({diffusion_model.in_channels})")
+        return conditioning, cc, ctx_shape
+
+    @torch.no_grad()
+    def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
+               mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0):
+        """conditioning with mode="concat": fp32 NC'[D]HW, model_input = cat([image, conditioning], dim=1) at every step; with
+        mode="crossattn": fp32 [N, tokens, cross_attention_dim], the model's `context` (train_ldm.py:349-365 passes neither).
+        noises: optional sequence with the z of every step (tests pin them); generator: torch generator for the per-step noise.
+        eta: the noise scale of a DDIMScheduler (0 = deterministic; no per-step noise is drawn); other schedulers ignore it."""
+        conditioning, cc, ctx_shape = self._conditioning(input_noise, diffusion_model, conditioning, mode)
         scheduler = scheduler or self.scheduler
         inter = []
 
@@ -238,8 +359,20 @@ class DiffusionInferer:
                 inter.append(x.clone())
 
         loop = self._loop(diffusion_model, scheduler, input_noise.shape, input_noise.device, cc, ctx_shape)
-        image = loop.run(input_noise.float(), noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning)
+        image = loop.run(input_noise.float(), noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning,
+                         eta=eta)
         return (image, inter) if save_intermediates else image
+
+    @torch.no_grad()
+    def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True):
+        """Image-to-noise DDIM inversion: DDIMScheduler.reversed_step over ascending timesteps in the fused loop of `sample` (same
+        captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler."""
+        scheduler = scheduler or self.scheduler
+        if not isinstance(scheduler, DDIMScheduler):
+            raise TypeError(f"invert needs a DDIMScheduler (reversed_step), not {type(scheduler).__name__}")
+        conditioning, cc, ctx_shape = self._conditioning(image, diffusion_model, conditioning, mode)
+        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape)
+        return loop.run(image.float(), use_graph=use_graph, conditioning=conditioning, reverse=True)
 
 
 class LatentDiffusionInferer(DiffusionInferer):
@@ -259,11 +392,17 @@ class LatentDiffusionInferer(DiffusionInferer):
 
     @torch.no_grad()
     def sample(self, input_noise, autoencoder_model, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100,
-               conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True):
+               conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0):
         out = super().sample(input_noise, diffusion_model, scheduler, save_intermediates, intermediate_steps, conditioning, mode, verbose,
-                             noises=noises, generator=generator, use_graph=use_graph)
+                             noises=noises, generator=generator, use_graph=use_graph, eta=eta)
         latent, inter = out if save_intermediates else (out, None)
         image = autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
         if save_intermediates:
             return image, [autoencoder_model.decode_stage_2_outputs(z / self.scale_factor) for z in inter]
         return image
+
+    @torch.no_grad()
+    def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True):
+        """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor)."""
+        latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
+        return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph)

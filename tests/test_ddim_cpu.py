@@ -1,0 +1,143 @@
+"""inferer.DDIMScheduler on the CPU against the fp64 restatement in tests/ddim_ref.py (third-party closed form, PARITY UNPINNED -- see
+its docstring): timesteps, the per-step rows in both directions, the identity with the DDPM posterior that the mathematics gives,
+the tensor-level step / reversed_step, and the C-ABI surface of the fused update."""
+import os
+import re
+
+import pytest
+import torch
+
+from tests import ddim_ref
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TRAIN = dict(schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)  # the schedule the reference trains with (train_ldm.py:74)
+
+
+def test_timesteps():
+    from medical_image_generation_amd.inferer import DDIMScheduler
+    sch = DDIMScheduler()
+    assert sch.num_inference_steps == 1000 and sch.timesteps.tolist() == list(range(999, -1, -1)) and sch.timesteps.dtype == torch.int64
+    sch.set_timesteps(10)
+    assert sch.timesteps.tolist() == [900, 800, 700, 600, 500, 400, 300, 200, 100, 0] and sch.timesteps.dtype == torch.int64
+    assert sch.num_inference_steps == 10
+    off = DDIMScheduler(steps_offset=1)
+    off.set_timesteps(10)
+    assert off.timesteps.tolist() == [901, 801, 701, 601, 501, 401, 301, 201, 101, 1]
+    with pytest.raises(ValueError):
+        sch.set_timesteps(2000)
+    with pytest.raises(ValueError):
+        DDIMScheduler(steps_offset=100).set_timesteps(10)  # 900 + 100 is no training timestep
+    assert sch.num_inference_steps == 10  # a refused call changes nothing
+    with pytest.raises(ValueError, match="unknown prediction_type"):
+        DDIMScheduler(prediction_type="sample")
+    with pytest.raises(ValueError, match="unknown schedule cosine"):
+        DDIMScheduler(schedule="cosine")
+
+
+def test_attributes_and_closed_forms():
+    from medical_image_generation_amd.inferer import DDIMScheduler, DDPMScheduler, betas
+    sch = DDIMScheduler(num_train_timesteps=250, **TRAIN)
+    assert torch.equal(sch.betas, betas(num_train_timesteps=250, **TRAIN)) and torch.equal(sch.alphas, 1.0 - sch.betas)
+    assert torch.equal(sch.alphas_cumprod, DDPMScheduler(num_train_timesteps=250, **TRAIN).alphas_cumprod)
+    assert sch.num_train_timesteps == 250 and sch.prediction_type == "epsilon" and sch.clip_sample is True
+    assert float(sch.final_alpha_cumprod) == 1.0 and float(sch.first_alpha_cumprod) == 0.0
+    assert float(DDIMScheduler(set_alpha_to_one=False, **TRAIN).final_alpha_cumprod) == float(DDIMScheduler(**TRAIN).alphas_cumprod[0])
+    g = torch.Generator().manual_seed(3)
+    x, n = torch.randn(3, 2, 4, 5, generator=g), torch.randn(3, 2, 4, 5, generator=g)
+    t = torch.tensor([0, 17, 249])
+    a = sch.alphas_cumprod.double()[t].reshape(-1, 1, 1, 1)
+    assert torch.allclose(sch.add_noise(x, n, t).double(), a.sqrt() * x + (1 - a).sqrt() * n, atol=1e-6)
+    assert torch.allclose(sch.get_velocity(x, n, t).double(), a.sqrt() * n - (1 - a).sqrt() * x, atol=1e-6)
+
+
+@pytest.mark.parametrize("n,eta,kw", [(5, 0.0, {}), (4, 0.5, {}), (1000, 1.0, {}), (4, 0.5, dict(steps_offset=1)),
+                                      (5, 0.0, dict(set_alpha_to_one=False, **TRAIN)), (8, 1.0, dict(set_alpha_to_one=False, **TRAIN))])
+def test_rows_match_the_restatement(n, eta, kw):
+    """Forward and reverse rows; rtol=1e-6, atol=1e-7 is the bound tests/test_schedule_cpu.py holds DDPMScheduler._coef to."""
+    from medical_image_generation_amd.inferer import DDIMScheduler
+    sch = DDIMScheduler(**kw)
+    sch.set_timesteps(n)
+    sched = {k: v for k, v in kw.items() if k in TRAIN}
+    acp, _ = ddim_ref.alphas_cumprod(1000, **sched)
+    assert sch.timesteps.tolist() == ddim_ref.timesteps(1000, n, kw.get("steps_offset", 0))
+    ref = dict(steps_offset=kw.get("steps_offset", 0), set_alpha_to_one=kw.get("set_alpha_to_one", True))
+    fwd, rev = sch.rows(eta), sch.rows(reverse=True)
+    assert fwd.dtype == torch.float32 and fwd.shape == (n, 5) and rev.dtype == torch.float32 and rev.shape == (n, 5)
+    assert torch.allclose(fwd.double(), ddim_ref.rows(acp, n, eta, **ref), rtol=1e-6, atol=1e-7)
+    assert torch.allclose(rev.double(), ddim_ref.rows(acp, n, reverse=True, **ref), rtol=1e-6, atol=1e-7)
+    assert float(rev[:, 4].abs().max()) == 0.0 and (eta > 0 or float(fwd[:, 4].abs().max()) == 0.0)
+    if ref["set_alpha_to_one"]:
+        assert fwd[-1].tolist()[2:] == [1.0, 0.0, 0.0]  # the last denoising step lands on the predicted x0
+    if n * (1000 // n) + ref["steps_offset"] >= 1000:
+        assert rev[-1].tolist()[2:] == [0.0, 1.0, 0.0]  # the last inversion step lands on pure noise
+
+
+def test_ddim_with_every_step_and_eta_one_is_the_ddpm_posterior():
+    """With n = T and eta = 1 the DDIM update r2 x0 + r3 eps + r4 z, with eps = (x_t - r0 x0) / r1, is the DDPM posterior with
+    "fixed_small" variance: r2 - r3 r0 / r1 = c_x0, r3 / r1 = c_xt, r4 = sigma for every t >= 1, to 1e-10 in fp64.  A factor-of-stride
+    or index slip in the previous level fails this by orders of magnitude.
+
+    The DDPM side is DDPMScheduler._coef's formulas evaluated in fp64.  Both sides take the scheduler's fp32 betas as fp64 numbers and
+    their fp64 cumulative product: the identity needs a_t = a_{t-1} (1 - beta_t), which the fp32 alphas_cumprod table holds to one
+    fp32 rounding only (6e-8 of a_t, i.e. up to 6e-4 of beta_t = 1e-4), so on that table it could not be checked below about 1e-3."""
+    from medical_image_generation_amd.inferer import DDPMScheduler
+    for kw in ({}, TRAIN):
+        _, b = ddim_ref.alphas_cumprod(1000, **kw)
+        assert b == DDPMScheduler(**kw).betas.double().tolist()  # the same inputs the product's table is built from
+        b = torch.tensor(b, dtype=torch.float64)
+        acp = torch.cumprod(1 - b, dim=0)
+        prev = torch.cat([torch.ones(1, dtype=torch.float64), acp[:-1]])
+        c_x0, c_xt = prev.sqrt() * b / (1 - acp), (1 - b).sqrt() * (1 - prev) / (1 - acp)
+        sigma = ((1 - prev) / (1 - acp) * b).clamp(min=1e-20).sqrt()
+        r = ddim_ref.rows(acp.tolist(), 1000, eta=1.0).flip(0)  # row t for timestep t
+        t = slice(1, None)
+        assert float((r[t, 2] - r[t, 3] * r[t, 0] / r[t, 1] - c_x0[t]).abs().max()) <= 1e-10
+        assert float((r[t, 3] / r[t, 1] - c_xt[t]).abs().max()) <= 1e-10
+        assert float((r[t, 4] - sigma[t]).abs().max()) <= 1e-10
+
+
+@pytest.mark.parametrize("clip", [True, False])
+@pytest.mark.parametrize("prediction_type", ["epsilon", "v_prediction"])
+def test_step_and_reversed_step_on_cpu_tensors(prediction_type, clip):
+    """atol=1e-5 (torch.allclose, as tests/test_inferer_gpu.py checks DDPMScheduler.step)."""
+    from medical_image_generation_amd.inferer import DDIMScheduler
+    sch = DDIMScheduler(prediction_type=prediction_type, clip_sample=clip)
+    sch.set_timesteps(10)
+    acp, _ = ddim_ref.alphas_cumprod(1000)
+    g = torch.Generator().manual_seed(11)
+    shape = (2, 3, 4, 6, 5)
+    x, m = torch.randn(shape, generator=g) * 1.5, torch.randn(shape, generator=g)
+    kw = dict(prediction_type=prediction_type, clip_sample=clip)
+    for t in (500, 100, 0):
+        prev, x0 = sch.step(m, t, x)
+        w_prev, w_x0 = ddim_ref.update(ddim_ref.forward_row(acp, t, 100), x, m, **kw)
+        assert prev.dtype == torch.float32 and torch.allclose(prev.double(), w_prev, atol=1e-5) and torch.allclose(x0.double(), w_x0, atol=1e-5)
+        # eta > 0: the noise is r4 * randn of the given generator
+        prev, x0 = sch.step(m, torch.tensor(t), x, eta=0.5, generator=torch.Generator().manual_seed(5))
+        z = torch.randn(shape, generator=torch.Generator().manual_seed(5))
+        row = ddim_ref.forward_row(acp, t, 100, eta=0.5)
+        w_prev, w_x0 = ddim_ref.update(row, x, m, z, **kw)
+        assert torch.allclose(prev.double(), w_prev, atol=1e-5) and torch.allclose(x0.double(), w_x0, atol=1e-5)
+        det, _ = ddim_ref.update(row[:4] + [0.0], x, m, **kw)
+        assert torch.allclose(prev.double() - det, row[4] * z.double(), atol=1e-5) and (row[4] > 1e-3) == (t > 0)
+    for t in (0, 500, 900):
+        post, x0 = sch.reversed_step(m, t, x)
+        w_post, w_x0 = ddim_ref.update(ddim_ref.reverse_row(acp, t, 100), x, m, **kw)
+        assert torch.allclose(post.double(), w_post, atol=1e-5) and torch.allclose(x0.double(), w_x0, atol=1e-5)
+
+
+def test_invert_needs_a_ddim_scheduler():
+    from medical_image_generation_amd.inferer import DDPMScheduler, DiffusionInferer
+    with pytest.raises(TypeError, match="DDIMScheduler"):
+        DiffusionInferer(DDPMScheduler()).invert(torch.zeros(1, 1, 8, 8, 8), None)
+
+
+def test_fused_update_is_declared_and_bound():
+    """The entry point is in the header and the binding with one argument list (tests/test_abi_cpu.py then checks the export)."""
+    from medical_image_generation_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
+    m = re.search(r"\bint mi_ddim_step\s*\(([^)]*)\)\s*;", hdr)
+    assert m and "mi_ddim_step" in _lib._SIGS
+    assert len(m.group(1).split(",")) == len(_lib._SIGS["mi_ddim_step"])
+    assert _lib._SIGS["mi_ddim_step"] == _lib._SIGS["mi_ddpm_step"]  # same argument types; rows / row_index in place of coef / t
+    assert _lib.ABI_VERSION >= 14

@@ -1,12 +1,15 @@
-"""Reverse-diffusion throughput of the C4 U-Net (128^3, batch 1): ms per denoising step (UNet forward + fused update, hipGraph)."""
-import os, sys, time
+"""Reverse-diffusion throughput of the C4 U-Net (128^3, batch 1): ms per denoising step (UNet forward + fused update, hipGraph) of the
+DDPM loop and of the DDIM loop (eta = 0: no per-step noise launch; eta = 1: noise at every step), taken in alternation in one process.
+usage: bench_sample.py [size=128] [steps=50] [repeats=5]"""
+import os, statistics, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import bench
-from medical_image_generation_amd.inferer import DDPMScheduler, DiffusionInferer
+from medical_image_generation_amd.inferer import DDIMScheduler, DDPMScheduler, DiffusionInferer
 from medical_image_generation_amd.unet import DiffusionModelUNet
 size = int(sys.argv[1]) if len(sys.argv) > 1 else 128
 nsteps = int(sys.argv[2]) if len(sys.argv) > 2 else 50
+repeats = int(sys.argv[3]) if len(sys.argv) > 3 else 5
 dev = torch.device("cuda")
 torch.manual_seed(0)
 net = DiffusionModelUNet(**bench.C4)
@@ -14,17 +17,23 @@ for p in net.parameters():
     if float(p.detach().abs().max()) == 0:
         torch.nn.init.normal_(p, std=0.02)
 net = net.to(dev).eval()
-sch = DDPMScheduler(num_train_timesteps=1000, schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)
-sch.set_timesteps(nsteps)
-inf = DiffusionInferer(sch)
+kw = dict(num_train_timesteps=1000, schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)
+runs = {"ddpm": (DDPMScheduler(**kw), {}), "ddim eta=0": (DDIMScheduler(**kw), {}), "ddim eta=1": (DDIMScheduler(**kw), {"eta": 1.0})}
 x = torch.randn((1, 1, size, size, size), device=dev)
-for graph in (True,):
-    img = inf.sample(x, net, sch, verbose=False, use_graph=graph)   # includes plan creation + capture
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    img = inf.sample(x, net, sch, verbose=False, use_graph=graph)
-    torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / nsteps
-    assert torch.isfinite(img).all()
-    print({"config": f"C4 sampling {size}^3", "hipgraph": graph, "ms_per_denoising_step": dt * 1e3, "voxels_per_s": size ** 3 / dt,
-           "s_per_1000_steps": dt * 1e3}, flush=True)
+infs, times = {}, {k: [] for k in runs}
+for name, (sch, extra) in runs.items():
+    sch.set_timesteps(nsteps)
+    infs[name] = DiffusionInferer(sch)
+    infs[name].sample(x, net, sch, verbose=False, **extra)   # includes plan creation + capture
+torch.cuda.synchronize()
+for _ in range(repeats):
+    for name, (sch, extra) in runs.items():
+        t0 = time.perf_counter()
+        img = infs[name].sample(x, net, sch, verbose=False, **extra)
+        torch.cuda.synchronize()
+        times[name].append((time.perf_counter() - t0) / nsteps)
+        assert torch.isfinite(img).all()
+for name, ts in times.items():
+    dt = statistics.median(ts)
+    print({"config": f"C4 sampling {size}^3", "scheduler": name, "hipgraph": True, "ms_per_denoising_step": dt * 1e3, "voxels_per_s": size ** 3 / dt,
+           "s_per_1000_steps": dt * 1e3, "ms_per_step_min_max": [min(ts) * 1e3, max(ts) * 1e3], "repeats": repeats}, flush=True)
