@@ -389,6 +389,16 @@ int mi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  * same fp32 values.  grad_sumsq NULL: no clipping (max_norm unused). */
 int mi_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* hparams,
                      int decoupled_weight_decay, const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t stream);
+/* mi_adam_ema_step_dev: mi_adam_step_dev plus an exponential moving average of the parameters in the same pass (one more array read
+ * and written, no second launch): after param[i] is final, ema[i] += (1 - d) * (param[i] - ema[i]).  d is uniform per launch and read
+ * from the device block, which has eight slots here: hparams[6] the decay, hparams[7] != 0 the warm-up d = min(decay, (1 + t) /
+ * (10 + t)) with t the incremented step count -- so a captured graph follows a changed decay.  param / exp_avg / exp_avg_sq come out
+ * bit-identical to mi_adam_step_dev.  ema: fp32 [n], NULL -> MI_ERR_BAD_ARG. */
+int mi_adam_ema_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, const float* hparams,
+                         int decoupled_weight_decay, const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t stream);
+/* a <-> b over fp32 buffers, in place (16-byte aligned pointers): the parameters and their moving average trade places, so every
+ * fixed pointer into the arena (captured graphs, conv plans) reads the average until the second call trades them back */
+int mi_swap_f32(float* a, float* b, int64_t n, hipStream_t stream);
 /* y += alpha * x over fp32 buffers: gradient accumulation over micro-batches (grad_accumulate_step, train_ldm.py:173-180) */
 int mi_axpy_f32(float* y, const float* x, float alpha, int64_t n, hipStream_t stream);
 /* x *= alpha: `latents * inferer.scale_factor` of the latent-diffusion step (train_ldm.py:157) */

@@ -120,6 +120,8 @@ _SIGS = {
     "mi_clip_grad_by_norm": [_p, _l, _p, _f, _p],
     "mi_adam_step": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _f, _f, _p, _p],
     "mi_adam_step_dev": [_p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
+    "mi_adam_ema_step_dev": [_p, _p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
+    "mi_swap_f32": [_p, _p, _l, _p],
     "mi_axpy_f32": [_p, _p, _f, _l, _p],
     "mi_scale_f32": [_p, _f, _l, _p],
     "mi_meter_bytes": [],
@@ -136,7 +138,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 14
+ABI_VERSION = 15
 
 
 def exported_symbols() -> list[str]:

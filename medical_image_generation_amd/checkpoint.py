@@ -13,6 +13,10 @@ GAN trainers (a `.D` discriminator with its own optimizer, `d_optimizer`) also w
 'discriminator_state_dict' (BatchNorm running buffers included), 'disc_optimizer_state_dict' (torch.optim.Adam layout over the
 discriminator's parameters) and, when a discriminator scheduler is given, 'disc_scheduler_state_dict'; load_model restores each one that
 is present (train_autoencoder.py:566-588).  Keys a scheduler adds to the parameter group ('initial_lr', ...) are carried both ways.
+
+A trainer that keeps averaged weights (`ema_decay=`) adds 'ema_state_dict' (the names and shapes of 'network_state_dict', trainable
+tensors from the shadow) and 'ema_decay'; without one the key set is unchanged.  The reference's loaders index the keys they know and
+ignore the rest, so they still read these files.
 """
 from __future__ import annotations
 
@@ -105,6 +109,9 @@ def save_model(trainer, results_path, epoch, validation_loss, scheduler=None, di
                   "optimizer_state_dict": optimizer_state_dict(trainer), "validation_loss": validation_loss}
     if scheduler:
         checkpoint["scheduler_state_dict"] = scheduler.state_dict()
+    if getattr(trainer, "ema", None) is not None:
+        checkpoint["ema_state_dict"] = trainer.ema_state_dict()
+        checkpoint["ema_decay"] = float(trainer.ema_decay)
     if getattr(trainer, "D", None) is not None:
         checkpoint["discriminator_state_dict"] = {k: v.detach().cpu() for k, v in trainer.D.state_dict().items()}
         checkpoint["disc_optimizer_state_dict"] = optimizer_state_dict(trainer.d_optimizer)
@@ -125,9 +132,18 @@ def save_model(trainer, results_path, epoch, validation_loss, scheduler=None, di
 def load_model(trainer, load_model_path, load_optimizer=True, lr_scheduler=None, for_training=False, disc_scheduler=None):
     """train_ldm.py:492-505 / train_autoencoder.py:566-591: every part present in the file is restored (the discriminator's only on a
     GAN trainer).  Parameters, moments and step counts are written in place and the hyperparameters reach the device block before the
-    next step, so this also holds for a trainer that was already captured.  Returns the epoch to resume at when for_training."""
+    next step, so this also holds for a trainer that was already captured.  Returns the epoch to resume at when for_training.
+    A trainer with averaged weights restores them from 'ema_state_dict' (in place), or restarts the average at the loaded parameters
+    when the file has none; the file's 'ema_decay' is informative, the trainer keeps its own.  Without a shadow the key is ignored."""
+    if getattr(trainer, "_ema_swapped", False):
+        raise RuntimeError("load_model inside ema_weights(): the arena holds the averaged weights; leave the context first")
     checkpoint = _load(load_model_path)
     trainer.model.load_state_dict(checkpoint["network_state_dict"])
+    if getattr(trainer, "ema", None) is not None:
+        if "ema_state_dict" in checkpoint:
+            trainer.load_ema_state_dict(checkpoint["ema_state_dict"])
+        else:
+            trainer.reset_ema()
     if load_optimizer:
         load_optimizer_state_dict(trainer, checkpoint["optimizer_state_dict"])
     if lr_scheduler and "scheduler_state_dict" in checkpoint:

@@ -62,6 +62,10 @@ __global__ void __launch_bounds__(256) k_adam(AdamArgs a) {
 // once per thread), so a captured graph follows a learning-rate schedule or a loaded checkpoint.  The loop body is k_adam's statement
 // for statement: the compiler then forms the same fused multiply-adds and the results are bit-identical for the same fp32 values
 // (an f32x4 restatement contracted differently and was not).
+// EMA: the same launch also moves a shadow of the parameters, e += (1 - d) * (p - e) on the final p (the lerp form keeps its accuracy
+// for d near 1).  d = hp[6], or min(hp[6], (1 + t) / (10 + t)) when hp[7] != 0 (warm-up on the incremented step count t): uniform per
+// launch, read from the device block like lr, so a captured graph follows a changed decay.  One body for both instantiations, and
+// the shadow statements come after the three stores: p / m / v of EMA = true are bit-identical to EMA = false.
 struct AdamDevArgs {
   float* p;
   const float* g;
@@ -73,8 +77,10 @@ struct AdamDevArgs {
   int decoupled;
   const float* sumsq;
   const float* step;
+  float* ema;  // EMA = true only
 };
 
+template <bool EMA>
 __global__ void __launch_bounds__(256) k_adam_dev(AdamDevArgs a) {
   const float lr = a.hp[0], beta1 = a.hp[1], beta2 = a.hp[2], eps = a.hp[3], weight_decay = a.hp[4];
   const float t = *a.step;
@@ -84,6 +90,15 @@ __global__ void __launch_bounds__(256) k_adam_dev(AdamDevArgs a) {
   if (a.sumsq) {
     float c = a.hp[5] / (a.grad_scale * sqrtf(*a.sumsq) + 1e-6f);
     clip = (c < 1.f ? c : 1.f) * a.grad_scale;
+  }
+  float one_minus_d = 0.f;
+  if constexpr (EMA) {
+    float d = a.hp[6];
+    if (a.hp[7] != 0.f) {
+      const float w = (1.f + t) / (10.f + t);
+      d = w < d ? w : d;
+    }
+    one_minus_d = 1.f - d;
   }
   for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < a.n; i += (int64_t)gridDim.x * 256) {
     float p = a.p[i], g = a.g[i] * clip, m = a.m[i], v = a.v[i];
@@ -97,6 +112,11 @@ __global__ void __launch_bounds__(256) k_adam_dev(AdamDevArgs a) {
     a.p[i] = p;
     a.m[i] = m;
     a.v[i] = v;
+    if constexpr (EMA) {
+      float e = a.ema[i];
+      e += one_minus_d * (p - e);
+      a.ema[i] = e;
+    }
   }
 }
 
@@ -113,6 +133,19 @@ __global__ void __launch_bounds__(256) k_axpy(f32x4* __restrict__ y, const f32x4
     y[i] = a;
   }
   if (blockIdx.x == 0 && (int)threadIdx.x < ntail) yt[threadIdx.x] += alpha * xt[threadIdx.x];
+}
+// a <-> b (the trainer's parameters and their moving average trade places around validation / sampling)
+__global__ void __launch_bounds__(256) k_swap(f32x4* a, f32x4* b, int64_t n4, float* at, float* bt, int ntail) {
+  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n4; i += (int64_t)gridDim.x * 256) {
+    f32x4 x = a[i], y = b[i];
+    a[i] = y;
+    b[i] = x;
+  }
+  if (blockIdx.x == 0 && (int)threadIdx.x < ntail) {
+    float x = at[threadIdx.x], y = bt[threadIdx.x];
+    at[threadIdx.x] = y;
+    bt[threadIdx.x] = x;
+  }
 }
 __global__ void __launch_bounds__(256) k_scale_by_clip(float* g, int64_t n, const float* sumsq, float max_norm) {
   float c = max_norm / (sqrtf(*sumsq) + 1e-6f);
@@ -156,10 +189,32 @@ int mi_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp
                      const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t st) {
   if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !hparams || !step_counter || !(grad_scale > 0.f)) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, st, step_counter);
-  AdamDevArgs a{param, grad, exp_avg, exp_avg_sq, n, hparams, grad_scale, decoupled_weight_decay, grad_sumsq, step_counter};
+  AdamDevArgs a{param, grad, exp_avg, exp_avg_sq, n, hparams, grad_scale, decoupled_weight_decay, grad_sumsq, step_counter, nullptr};
   int grid = (int)((n + 255) / 256);
   grid = grid > 4096 ? 4096 : grid;
-  hipLaunchKernelGGL(k_adam_dev, dim3(grid), dim3(256), 0, st, a);
+  hipLaunchKernelGGL(k_adam_dev<false>, dim3(grid), dim3(256), 0, st, a);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+
+int mi_adam_ema_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, float* ema, int64_t n, const float* hparams,
+                         int decoupled_weight_decay, const float* grad_sumsq, float grad_scale, float* step_counter, hipStream_t st) {
+  if (n <= 0 || !param || !grad || !exp_avg || !exp_avg_sq || !ema || !hparams || !step_counter || !(grad_scale > 0.f)) return MI_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_step_inc, dim3(1), dim3(1), 0, st, step_counter);
+  AdamDevArgs a{param, grad, exp_avg, exp_avg_sq, n, hparams, grad_scale, decoupled_weight_decay, grad_sumsq, step_counter, ema};
+  int grid = (int)((n + 255) / 256);
+  grid = grid > 4096 ? 4096 : grid;
+  hipLaunchKernelGGL(k_adam_dev<true>, dim3(grid), dim3(256), 0, st, a);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+
+int mi_swap_f32(float* a, float* b, int64_t n, hipStream_t st) {
+  if (n <= 0 || !a || !b || ((uintptr_t)a & 15) || ((uintptr_t)b & 15)) return MI_ERR_BAD_ARG;
+  int64_t n4 = n / 4;
+  int grid = (int)((n4 + 255) / 256);
+  grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
+  hipLaunchKernelGGL(k_swap, dim3(grid), dim3(256), 0, st, (f32x4*)a, (f32x4*)b, n4, a + n4 * 4, b + n4 * 4, (int)(n - n4 * 4));
   MI_CHECK_LAUNCH();
   return 0;
 }

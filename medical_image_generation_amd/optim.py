@@ -7,6 +7,10 @@ One parameter group holds the module's parameters in `parameters()` order, with 
 block {lr, beta1, beta2, eps, weight_decay, max_norm}; before every launch or graph replay the group is compared with the values last
 pushed and the block is rewritten when they differ -- one host-to-device copy on the current stream, never inside a capture.  That is
 how a replayed optimizer graph follows `scheduler.step()`, a changed `trainer.lr` or a loaded checkpoint.
+
+With `ema=` (fp32 [arena.n_trainable]) the update also moves an exponential moving average of the parameters in the same launch
+(mi_adam_ema_step_dev).  Whether a shadow exists is fixed when a graph is captured; `ema_decay` and `ema_warmup` are the last two slots
+of the device block and travel through push() like lr.
 """
 from __future__ import annotations
 
@@ -22,12 +26,17 @@ class FusedAdam(torch.optim.Optimizer):
 
     model / arena: a HipModule and its ParamArena; exp_avg, exp_avg_sq: fp32 [arena.n_trainable]; step_count: fp32 [1] on the device.
     grad_scale: 1 / world (the gradient buffer holds the SUM over data-parallel ranks).  step() launches the update eagerly;
-    step(replay=graph) replays a captured graph that holds launch() instead.  Both push changed hyperparameters first."""
+    step(replay=graph) replays a captured graph that holds launch() instead.  Both push changed hyperparameters first.
+    ema: fp32 [arena.n_trainable] or None -- the shadow e += (1 - d) * (p - e) the update kernel moves along; d = ema_decay, or
+    min(ema_decay, (1 + step) / (10 + step)) with ema_warmup."""
 
     def __init__(self, model, arena, exp_avg, exp_avg_sq, step_count, lr, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
-                 decoupled=False, max_grad_norm=None, grad_scale=1.0):
+                 decoupled=False, max_grad_norm=None, grad_scale=1.0, ema=None, ema_decay=0.0, ema_warmup=False):
         self.model, self.arena = model, arena
         self.exp_avg, self.exp_avg_sq, self.step_count = exp_avg, exp_avg_sq, step_count
+        if ema is not None and (ema.dtype != F32 or ema.shape != exp_avg.shape or ema.device != exp_avg.device or not ema.is_contiguous()):
+            raise ValueError("ema must be a contiguous fp32 [arena.n_trainable] tensor on the moments' device")
+        self.ema, self.ema_decay, self.ema_warmup = ema, ema_decay, bool(ema_warmup)
         self.decoupled = bool(decoupled)
         self.max_grad_norm = max_grad_norm
         self.grad_scale = float(grad_scale)
@@ -37,7 +46,7 @@ class FusedAdam(torch.optim.Optimizer):
         self._ready = False
         super().__init__(list(model.parameters()), defaults)
         self._ready = True
-        self.hparams = torch.zeros(8, dtype=F32, device=exp_avg.device)  # {lr, beta1, beta2, eps, weight_decay, max_norm, -, -}
+        self.hparams = torch.zeros(8, dtype=F32, device=exp_avg.device)  # {lr, beta1, beta2, eps, weight_decay, max_norm, ema decay, ema warm-up}
         self.sumsq = torch.zeros(1, dtype=F32, device=exp_avg.device)
         self._pushed = None
 
@@ -80,6 +89,16 @@ class FusedAdam(torch.optim.Optimizer):
         self.param_groups[0]["weight_decay"] = float(v)
 
     @property
+    def ema_decay(self):
+        return self._ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, v):
+        if not 0.0 <= float(v) <= 1.0:
+            raise ValueError(f"ema_decay must lie in [0, 1], got {v}")
+        self._ema_decay = float(v)
+
+    @property
     def clip(self) -> bool:
         return self.max_grad_norm is not None and self.max_grad_norm > 0
 
@@ -88,7 +107,7 @@ class FusedAdam(torch.optim.Optimizer):
         if isinstance(g["lr"], torch.Tensor):
             raise TypeError("FusedAdam takes a float lr (its kernel reads the value from its own device block)")
         return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-                float(self.max_grad_norm) if self.clip else 0.0)
+                float(self.max_grad_norm) if self.clip else 0.0, float(self.ema_decay), 1.0 if self.ema_warmup else 0.0)
 
     def push(self):
         """Write the device hyperparameter block if the group changed since the last push (current stream, outside any capture)."""
@@ -97,18 +116,21 @@ class FusedAdam(torch.optim.Optimizer):
             return
         if self.hparams.is_cuda and torch.cuda.is_current_stream_capturing():
             raise RuntimeError("FusedAdam.push() inside a graph capture: push before capturing")
-        self.hparams[:6].copy_(torch.tensor(vals, dtype=F32))
+        self.hparams.copy_(torch.tensor(vals, dtype=F32))
         self._pushed = vals
 
     def launch(self):
         """The kernels of one update on the current stream (capturable): squared gradient norm when clipping, then Adam[W] reading the
-        device block.  Does not push."""
+        device block (and moving the shadow when there is one).  Does not push."""
         a = self.arena
         n = a.n_trainable
         if self.clip:
             call("mi_sumsq_f32", ptr(a.grad), n, ptr(self.sumsq), 0)
-        call("mi_adam_step_dev", ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), n, ptr(self.hparams), int(self.decoupled),
-             ptr(self.sumsq) if self.clip else None, self.grad_scale, ptr(self.step_count))
+        tail = (n, ptr(self.hparams), int(self.decoupled), ptr(self.sumsq) if self.clip else None, self.grad_scale, ptr(self.step_count))
+        if self.ema is None:
+            call("mi_adam_step_dev", ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), *tail)
+        else:
+            call("mi_adam_ema_step_dev", ptr(a.data), ptr(a.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self.ema), *tail)
 
     @torch.no_grad()
     def step(self, closure=None, replay=None):

@@ -20,9 +20,14 @@ AutoEncoder.validate_one_epoch, train_autoencoder.py:438-467; adapt_kl_loss_weig
 `ValidationMeter` that keeps the epoch's running mean on the device, so a validation epoch costs ONE host synchronisation
 (`meter.mean()`, the number checkpoint.save_model takes as `validation_loss`: train_ldm.py:466-491, train_autoencoder.py:533-564).
 Nothing the train step owns is written.
+
+Averaged weights (`ema_decay=`; not in the reference): the optimizer launch also moves an exponential moving average of the trainable
+parameters (`trainer.ema`), and `with trainer.ema_weights():` trades it with the parameters in place, so validation, sampling and
+state_dict() read the average through the pointers they already hold.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 
@@ -124,7 +129,7 @@ class _ArenaTrainer:
     overlap has been rehearsed with gloo ranks and with one-rank RCCL groups only: DESIGN.md section 6)."""
 
     def __init__(self, model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
-                 grad_accumulate_step=1, overlap=None):
+                 grad_accumulate_step=1, overlap=None, ema_decay=None, ema_warmup=False):
         self.model = model
         self.device = torch.device(device or "cuda")
         self.decoupled = optimizer == "AdamW"
@@ -146,8 +151,13 @@ class _ArenaTrainer:
         self.step_count = torch.zeros(1, dtype=F32, device=self.device)
         # the torch.optim face of the fused optimizer: torch LR schedulers bind to it (train_ldm.py:124-130); lr / betas / eps /
         # weight_decay / max_grad_norm below are views of its parameter group
+        # the shadow starts as a copy of the (broadcast) parameters, so the average needs no bias correction; ranks then stay identical
+        # without a collective, because they apply identical updates
+        self.ema = None if ema_decay is None else self.arena.data[:n].clone()
+        self._ema_swapped = False  # inside ema_weights(): arena.data holds the average, self.ema the parameters
         self.optimizer = FusedAdam(model, self.arena, self.exp_avg, self.exp_avg_sq, self.step_count, lr, betas, eps, weight_decay,
-                                   self.decoupled, max_grad_norm, 1.0 / self.world)
+                                   self.decoupled, max_grad_norm, 1.0 / self.world, ema=self.ema,
+                                   ema_decay=0.0 if ema_decay is None else ema_decay, ema_warmup=ema_warmup)
         self.sumsq = self.optimizer.sumsq
         self.loss = torch.zeros(1, dtype=F32, device=self.device)
         self._accum = None       # fp32 [n_trainable]: sum of the gradients of the pending micro-steps (grad_accumulate_step > 1)
@@ -173,6 +183,76 @@ class _ArenaTrainer:
     @max_grad_norm.setter
     def max_grad_norm(self, v):
         self.optimizer.max_grad_norm = v
+
+    # ------------------------------------------------------------------ averaged weights
+    @property
+    def ema_decay(self):
+        """The decay of the shadow (None without one); like lr it may change between steps or replays."""
+        return None if self.ema is None else self.optimizer.ema_decay
+
+    @ema_decay.setter
+    def ema_decay(self, v):
+        if self.ema is None:
+            raise RuntimeError("this trainer was built without ema_decay: whether a shadow exists is fixed at construction")
+        self.optimizer.ema_decay = v
+
+    ema_warmup = property(lambda self: self.optimizer.ema_warmup, lambda self, v: setattr(self.optimizer, "ema_warmup", bool(v)))
+
+    def _need_ema(self):
+        if self.ema is None:
+            raise RuntimeError("this trainer keeps no averaged weights: construct it with ema_decay=")
+
+    def _not_swapped(self, what):
+        if self._ema_swapped:
+            raise RuntimeError(f"{what} inside ema_weights(): the arena holds the averaged weights; leave the context first")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the arena's trainable prefix holds the averaged weights (and `trainer.ema` the parameters): one in-place
+        exchange on entry and one on exit, so no pointer changes -- captured graphs, conv plans (they repack from the arena per run or
+        replay), validate() / validate_graph(), inferer.sample() / invert() on trainer.model and model.state_dict() all read the
+        average.  The statically unused tail is not touched.  Training calls and load_model are refused inside."""
+        self._need_ema()
+        self._not_swapped("ema_weights()")
+        if self.model._arena is not self.arena:
+            raise RuntimeError("the model's parameter arena was rebuilt after this trainer was created: the averaged weights belong to "
+                               "the old buffers; create a new trainer")
+        n = self.arena.n_trainable
+        call("mi_swap_f32", ptr(self.arena.data), ptr(self.ema), n)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            call("mi_swap_f32", ptr(self.arena.data), ptr(self.ema), n)
+            self._ema_swapped = False
+
+    def ema_state_dict(self):
+        """The network's state_dict() (names, shapes; CPU tensors) with every trainable tensor taken from the shadow; tensors that
+        never receive a gradient and buffers come from the network.  No exchange: usable at any time."""
+        self._need_ema()
+        a = self.arena
+        flat = (self.ema if not self._ema_swapped else a.data[:a.n_trainable]).detach().cpu()
+        trainable = {n for n, _, t in self.model._entries if t}
+        return {k: (a.view(k, flat).clone() if k in trainable else v.detach().cpu().clone()) for k, v in self.model.state_dict().items()}
+
+    def load_ema_state_dict(self, sd):
+        """Restore the shadow from an ema_state_dict(), in place (a captured optimizer graph keeps pointing at it)."""
+        self._need_ema()
+        self._not_swapped("load_ema_state_dict()")
+        a = self.arena
+        flat = self.ema.detach().cpu()
+        for name, shape, t in self.model._entries:
+            if t:
+                if name not in sd or tuple(sd[name].shape) != tuple(shape):
+                    raise ValueError(f"averaged weights: {name} is missing or has another shape than {tuple(shape)}")
+                a.view(name, flat).copy_(sd[name].to(F32))
+        self.ema.copy_(flat)
+
+    def reset_ema(self):
+        """shadow := current parameters."""
+        self._need_ema()
+        self._not_swapped("reset_ema()")
+        self.ema.copy_(self.arena.data[:self.arena.n_trainable])
 
     # ------------------------------------------------------------------ pieces
     def _forward(self, *inputs):
@@ -222,6 +302,7 @@ class _ArenaTrainer:
 
     def optimizer_step(self):
         """clip_grad_norm_ + Adam[W] over the arena (self.optimizer.step(): pushes changed hyperparameters, then launches)."""
+        self._not_swapped("optimizer_step()")
         self.optimizer.step()
 
     @staticmethod
@@ -253,6 +334,7 @@ class _ArenaTrainer:
         """One (micro-)step, eager; returns the (device) loss tensor of this micro-batch without synchronising.  With
         grad_accumulate_step = k the optimizer runs on every k-th call (or when last_in_epoch, T-LDM:173); the data-parallel
         exchange happens on that boundary micro-step only."""
+        self._not_swapped("step()")
         boundary = (self._micro + 1) % self.grad_accumulate_step == 0 or last_in_epoch
         ex = self._exchange() if self._exchanging() and boundary else None
         # the early segment may leave at the cut only when no pending micro-step sum has to be folded in first
@@ -269,6 +351,7 @@ class _ArenaTrainer:
         """Capture the step as hipGraphs around static input buffers; call step_graph() afterwards.  Graphs: forward + the backward up
         to the cut, the rest of the backward (only when there is something to overlap: world > 1), the optimizer.  RCCL is never
         inside a capture: the all-reduces are issued between the replays, the early segment's concurrently with the second graph."""
+        self._not_swapped("capture()")
         if self.grad_accumulate_step != 1:
             raise RuntimeError("hipGraph capture covers grad_accumulate_step == 1; use step() for accumulation")
         static = tuple(None if t is None else t.clone() for t in inputs)  # (None: an optional input that is not used)
@@ -378,6 +461,7 @@ class _ArenaTrainer:
 
     def step_graph(self, *inputs):
         """Replay; inputs given (positionally, None = keep) are copied into the static buffers first."""
+        self._not_swapped("step_graph()")
         assert self._graph, "call capture() first"
         self._load_static(self._static, inputs, "capture()", "create a new trainer (or call capture() again)")
         ex = self._exchange() if self._exchanging() else None
@@ -404,9 +488,10 @@ class DDPMTrainer(_ArenaTrainer):
     in_channels = C + C' -- and the model predicts x0's C channels (out_channels = C), compared with x0's noise."""
 
     def __init__(self, model, lr=2e-5, optimizer="AdamW", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
-                 schedule: DDPMSchedule | None = None, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, overlap=None):
+                 schedule: DDPMSchedule | None = None, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, overlap=None,
+                 ema_decay=None, ema_warmup=False):
         super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
-                         grad_accumulate_step, overlap)
+                         grad_accumulate_step, overlap, ema_decay, ema_warmup)
         self.schedule = schedule or DDPMSchedule(device=self.device)
 
     def _check_inputs(self, x0, noise, timesteps, class_labels, context, condition):
@@ -579,9 +664,9 @@ class AETrainer(_ArenaTrainer):
 
     def __init__(self, model, lr=5e-5, optimizer="Adam", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  kl_weight=1e-7, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, extra_loss=None, overlap=None,
-                 perceptual=None, perc_weight=0.125):
+                 perceptual=None, perc_weight=0.125, ema_decay=None, ema_warmup=False):
         super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
-                         grad_accumulate_step, overlap)
+                         grad_accumulate_step, overlap, ema_decay, ema_warmup)
         self.kl_weight = float(kl_weight)
         self.extra_loss = extra_loss
         self.reconstruction = None
@@ -710,7 +795,8 @@ class AEGANTrainer(AETrainer):
         self.d_exp_avg = torch.zeros(n, dtype=F32, device=self.device)
         self.d_exp_avg_sq = torch.zeros(n, dtype=F32, device=self.device)
         self.d_step_count = torch.zeros(1, dtype=F32, device=self.device)
-        # torch.optim.Adam(discriminator.parameters(), lr=d_lr) (T-AE:471): the generator's betas / eps / clip norm, no weight decay
+        # torch.optim.Adam(discriminator.parameters(), lr=d_lr) (T-AE:471): the generator's betas / eps / clip norm, no weight decay;
+        # no averaged weights either: only the autoencoder is sampled from
         self.d_optimizer = FusedAdam(discriminator, self.d_arena, self.d_exp_avg, self.d_exp_avg_sq, self.d_step_count, d_lr, self.betas,
                                      self.eps, 0.0, False, self.max_grad_norm, 1.0 / self.world)
         self.d_sumsq = self.d_optimizer.sumsq
