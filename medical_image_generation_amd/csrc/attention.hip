@@ -435,10 +435,8 @@ constexpr int kMaxSplit = 8;
 void pick_split(int B, int heads, int S, int& nsplit, int& tps) {
   const int base = (S + 127) / 128 * B * heads, ntiles = (S + 63) / 64;
   int want = 512 / (base > 0 ? base : 1);
-  static const int env = [] { const char* e = getenv("MI_ATTN_SPLIT"); return e ? atoi(e) : 0; }();
-  if (env > 0) want = env;
   want = want < 1 ? 1 : (want > kMaxSplit ? kMaxSplit : want);
-  if (!env && want > ntiles / 4) want = ntiles / 4 > 0 ? ntiles / 4 : 1;
+  if (want > ntiles / 4) want = ntiles / 4 > 0 ? ntiles / 4 : 1;
   tps = (ntiles + want - 1) / want;
   nsplit = (ntiles + tps - 1) / tps;
 }

@@ -371,10 +371,8 @@ constexpr int kMaxSplit = 8;
 void pick_split(int B, int heads, int S, int& nsplit, int& tps) {
   const int base = (S + 63) / 64 * B * heads, ntiles = (S + 31) / 32;
   int want = 512 / (base > 0 ? base : 1);
-  static const int env = [] { const char* e = getenv("MI_ATTNW_SPLIT"); return e ? atoi(e) : 0; }();
-  if (env > 0) want = env;
   want = want < 1 ? 1 : (want > kMaxSplit ? kMaxSplit : want);
-  if (!env && want > ntiles / 8) want = ntiles / 8 > 0 ? ntiles / 8 : 1;
+  if (want > ntiles / 8) want = ntiles / 8 > 0 ? ntiles / 8 : 1;
   tps = (ntiles + want - 1) / want;
   nsplit = (ntiles + tps - 1) / tps;
 }
@@ -404,7 +402,7 @@ static_assert(lds_bwd<256>() <= 160 * 1024 && lds_bwd<384>() <= 160 * 1024, "LDS
 namespace mi_attn {
 
 bool attnw_supported(int C, int heads) {
-  static const int on = [] { const char* e = getenv("MI_ATTN_WIDE"); return e ? atoi(e) : 1; }();  // 0: materialised path (A/B runs)
+  static const int on = mi_env_int("MI_ATTN_WIDE", 1);  // 0: materialised path (A/B runs)
   if (!on || heads <= 0 || C % heads) return false;
   const int d = C / heads;
   return d == 512 || d == 768;

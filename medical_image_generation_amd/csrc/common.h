@@ -105,6 +105,12 @@ static inline hipError_t mi_zero_fill_f32(float* x, int64_t ld, int rows, int co
 // Ablation knobs (MI_C27_DBG, MI_CPH_DBG, MI_WGRAD_DBG, MI_IGEMM_DBG) switch parts of a kernel off and make it compute GARBAGE: they are
 // read in the diagnostic builds only (`make diag` / `make phdiag`: -DMI_DIAG_KNOBS); the shipped library ignores them.
 #include <stdlib.h>
+// Route switches (DESIGN.md section 5 lists them; tests/test_knobs_cpu.py checks the list): the only way the shipped library reads the
+// environment.  One site per name: `static const int x = mi_env_int("MI_...", dflt);`
+static inline int mi_env_int(const char* name, int dflt) {
+  const char* v = getenv(name);
+  return v ? atoi(v) : dflt;
+}
 static inline int mi_diag_knob(const char* name) {
 #ifdef MI_DIAG_KNOBS
   const char* v = getenv(name);

@@ -1966,24 +1966,21 @@ __global__ void __launch_bounds__(256) k_wgrad_reduce_up(const float* __restrict
   for (int e = threadIdx.x; e < nci * 27; e += 256) row[e] += outp[e / 27][e % 27];
 }
 
-int env_int(const char* name, int dflt);
 // cs: the conv's column-sum partials to fold in the same launch (cs.part == nullptr: none)
 inline void launch_wgrad_reduce(const float* part, int64_t split_stride, int nsplit, const int* uitems, int nitems, float* dw, int Co_t, int Ci_t,
                                 int KT, const int* pair_off, int npairs, CsReduce cs, hipStream_t st) {
-  static const int rows_kernel = env_int("MI_WGRAD_REDUCE_ROWS", 1);
   cs.nbx = (cs.Cout + 31) / 32;
   const int extra = cs.part ? cs.nbx * cs.N : 0;
   if (nsplit >= 32)
     hipLaunchKernelGGL(k_wgrad_reduce<8>, dim3(nitems * 32 + extra), dim3(256), 0, st, part, split_stride, nsplit, uitems, nitems, dw, Co_t, Ci_t, KT,
                        cs, nitems * 32);
-  else if (rows_kernel && KT <= 32 && npairs >= 8) {
+  else if (KT <= 32 && npairs >= 8) {
     // rows of a (cout block, cin chunk) pair per block.  Same-box (profiles/r04a_ab_reduce_rr*.log): the latent UNet (256-576 pairs per layer:
     // 8-18 k one-row blocks) 56.25 ms with 1, 55.85 with 2, 55.74 with 4, 56.17 with 8; the C4 net (16-64 pairs) 21.37 with 1, 21.49 with 4:
-    // few pairs need every block they can get.  MI_WGRAD_REDUCE_RR overrides.
-    static const int rr_env = env_int("MI_WGRAD_REDUCE_RR", 0);
-    const int rr = rr_env > 0 ? rr_env : (npairs >= 128 ? 4 : 1);
-    auto kr = rr >= 8 ? k_wgrad_reduce_rows<8> : rr >= 4 ? k_wgrad_reduce_rows<4> : rr >= 2 ? k_wgrad_reduce_rows<2> : k_wgrad_reduce_rows<1>;
-    const int gpp = 32 / (rr >= 8 ? 8 : rr >= 4 ? 4 : rr >= 2 ? 2 : 1);
+    // few pairs need every block they can get.
+    const bool rr4 = npairs >= 128;
+    auto kr = rr4 ? k_wgrad_reduce_rows<4> : k_wgrad_reduce_rows<1>;
+    const int gpp = rr4 ? 8 : 32;  // blocks per pair: 32 rows / rows per block
     hipLaunchKernelGGL(kr, dim3(npairs * gpp + extra), dim3(256), 0, st, part, split_stride, nsplit, uitems, pair_off, npairs, dw, Co_t, Ci_t, KT,
                        cs, npairs * gpp);
   }
@@ -2025,8 +2022,8 @@ Geom make_geom(int VB, int Do, int Ho, int Wo, const int halo[3], int N, int vox
   g.lds_bytes = g.HD * g.slice;
   g.tilesD = (Do + g.TD - 1) / g.TD; g.tilesH = (Ho + g.TH - 1) / g.TH; g.tilesW = (Wo + g.TW - 1) / g.TW;
   (void)N;
-  static const int hb_env = env_int("MI_TILE_HB", 2);  // rows of tiles per h-block of the tile walk (conv_common.h: tile_origin)
-  g.hb = (hb_env > 1 && g.tilesD > 1 && g.tilesH % hb_env == 0) ? hb_env : 1;
+  const int hb = 2;  // rows of tiles per h-block of the tile walk (conv_common.h: tile_origin)
+  g.hb = (g.tilesD > 1 && g.tilesH % hb == 0) ? hb : 1;
   return g;
 }
 
@@ -2178,11 +2175,6 @@ void free_tables(Tables& T) {
   if (T.d_wpk) (void)hipFree(T.d_wpk);
 }
 
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Bytes of a bf16 tensor [N][d][h][w] at channel pitch cs (> 0) when they fit the 32-bit range of a buffer descriptor, else 0.  What 0
 // means is the caller's: "unbounded" for some fields, MI_ERR_UNSUPPORTED for others.
 unsigned span32(int N, int d, int h, int w, int cs) {
@@ -2208,20 +2200,17 @@ int conv_args_tables(ConvArgs& a, const Tables& T, const Geom& g, int& ntiles) {
 
 // Weight-gradient kernels (k_conv_wgrad[2,3], k_wgrad_up): one workgroup per (pair, split); from 8 splits on, XCD-aware placement
 unsigned wgrad_grid(int npairs, int nsplit) { return nsplit >= 8 ? npairs * ((nsplit + 7) / 8) * 8 : npairs * nsplit; }
-bool wgrad_contig(int ntiles, int nsplit) {
-  static const int contig_env = env_int("MI_WGRAD_CONTIG", 1);
-  return contig_env && (ntiles % 8 == 0) && (nsplit % 8 == 0) && nsplit <= ntiles;
-}
+bool wgrad_contig(int ntiles, int nsplit) { return (ntiles % 8 == 0) && (nsplit % 8 == 0) && nsplit <= ntiles; }
 // Number of splits of the tile range.  One workgroup per CU (112 KB of LDS each), and workgroup i of a launch goes to XCD i % 8: an XCD
 // that is dealt more than its 32 CUs' worth runs a second round.  Rounding 256 / npairs UP (what this did) deals 33 workgroups to five
 // XCDs for 3 pairs (96 -> 32), and the launch takes twice as long: 554 us where 32 -> 32, a third of the work, takes 123.  Cost of a
-// split, in hundredths of a tile time = 100 x rounds x (tiles per workgroup + fixed_tiles) + slab_term per split; ties go to the coarser split.
-int pick_nsplit(int ntiles, int npairs, int fixed_tiles, int64_t slab_term) {
+// split, in tile times = rounds x (tiles per workgroup + fixed_tiles); ties go to the coarser split.
+int pick_nsplit(int ntiles, int npairs, int fixed_tiles) {
   int nsplit = 1;
   int64_t best = -1;
   for (int ns = 1; ns <= 256 && ns <= ntiles; ++ns) {
     const int per_xcd = ns >= 8 ? npairs * ((ns + 7) / 8) : (npairs * ns + 7) / 8;  // (wgrad_grid)
-    const int64_t rounds = (per_xcd + 31) / 32, cost = 100 * rounds * ((ntiles + ns - 1) / ns + fixed_tiles) + slab_term * ns;
+    const int64_t rounds = (per_xcd + 31) / 32, cost = rounds * ((ntiles + ns - 1) / ns + fixed_tiles);
     if (best < 0 || cost < best) { best = cost; nsplit = ns; }
   }
   return nsplit;
@@ -2265,17 +2254,10 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
 }
 
 int launch_igemm_any(const ConvArgs& a, int NCB, int mode, int ntiles, int ny, hipStream_t st) {
-  static const int wps2 = env_int("MI_CONV_NCB2_WPS", 2);  // tuning knob for the 64-cout-per-workgroup variant
-  if (mode == 1) {
-    if (NCB == 2) return wps2 == 1 ? launch_igemm<2, 2, 3, 1, 1>(a, ntiles, ny, st) : launch_igemm<2, 2, 2, 2, 1>(a, ntiles, ny, st);
-    static const int ring1 = env_int("MI_CONV_NCB1_RING", 3);  // weight-fragment ring depth (taps) of the 32-cout variant
-    return ring1 == 3 ? launch_igemm<1, 2, 3, 2, 1>(a, ntiles, ny, st) : launch_igemm<1, 2, 6, 2, 1>(a, ntiles, ny, st);
-  }
-  if (mode == 2) {
-    if (NCB == 2) return wps2 == 1 ? launch_igemm<2, 2, 3, 1, 2>(a, ntiles, ny, st) : launch_igemm<2, 2, 2, 2, 2>(a, ntiles, ny, st);
-    static const int ring1 = env_int("MI_CONV_NCB1_RING", 3);
-    return ring1 == 3 ? launch_igemm<1, 2, 3, 2, 2>(a, ntiles, ny, st) : launch_igemm<1, 2, 6, 2, 2>(a, ntiles, ny, st);
-  }
+  // <NCB, VB, RING, WPS, MODE>: two workgroups per CU everywhere; weight-fragment ring of 2 taps in the 64-cout-per-workgroup variant, of 3
+  // taps in the 32-cout variant
+  if (mode == 1) return NCB == 2 ? launch_igemm<2, 2, 2, 2, 1>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 2, 1>(a, ntiles, ny, st);
+  if (mode == 2) return NCB == 2 ? launch_igemm<2, 2, 2, 2, 2>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 2, 2>(a, ntiles, ny, st);
   if (NCB == 2) return launch_igemm<2, 2, 2, 2, 0>(a, ntiles, ny, st);
   return launch_igemm<1, 2, 4, 2, 0>(a, ntiles, ny, st);
 }
@@ -2373,9 +2355,7 @@ int upconv_wgrad_tables(mi_conv_plan* P) {
   const int npairs = ny * nch * 2;  // (cout block, cin chunk, d-parity half of the phases)
   P->wg_split_stride = (int64_t)ny * nch * 64 * 1024;
   const int ntiles = P->N * g.tilesD * g.tilesH * g.tilesW;
-  int nsplit = pick_nsplit(ntiles, npairs, 2, 0);  // (a tile here is 8 phase steps)
-  static const int ns_env = env_int("MI_WGU_NSPLIT", 0);
-  if (ns_env > 0 && ns_env <= ntiles) nsplit = ns_env;
+  int nsplit = pick_nsplit(ntiles, npairs, 2);  // (a tile here is 8 phase steps)
   while (nsplit > 1 && (int64_t)nsplit * P->wg_split_stride * 4 > (256ll << 20)) nsplit /= 2;
   P->wg_nsplit = nsplit;
   if (hipMalloc((void**)&P->d_part, (size_t)nsplit * P->wg_split_stride * 4) != hipSuccess) return (int)hipErrorOutOfMemory;
@@ -2428,10 +2408,8 @@ int conv_plan_routes(mi_conv_plan* P, const int halo_f[3], const int halo_d[3]) 
   // odd multiple of 32 pads its last workgroup row with 32 dead channels: for 96 that is a third more MFMAs than needed (the data
   // gradient of the 96 -> 32 conv of the finest up-block: 434 us as 64 + 32(+32 dead), ~345 as 3 x 32)
   P->ncb_fwd = Cout > 32 && Cout != 96 ? 2 : 1;
-  // only the 32-channel variant carries the GroupNorm sums in its epilogue (above): up to this many output channels the forward runs
-  // as rows of 32 so that the consumer's statistics pass disappears (A/B knob; 32 = the plain rule)
-  static const int ncb1_max = env_int("MI_NCB1_FWD_MAXC", 32);
-  if (Cout <= ncb1_max && (Cout % 32) == 0) P->ncb_fwd = 1;
+  // (only the 32-channel variant carries the GroupNorm sums in its epilogue; running 64- / 128-channel forwards as rows of 32 so that the
+  // consumer's statistics pass disappears was measured slower: EXPERIMENTS.md, round 3 (iv))
   P->ncb_dg = Cin > 32 && Cin != 96 ? 2 : 1;
   // few tiles (16^3 levels): 64 output channels per workgroup would leave most CUs without a workgroup -> 32 per workgroup
   const int64_t tiles = (int64_t)N * ((od[0] + 3) / 4) * ((od[1] + 7) / 8) * ((od[2] + 7) / 8);
@@ -2443,20 +2421,20 @@ int conv_plan_routes(mi_conv_plan* P, const int halo_f[3], const int halo_d[3]) 
   P->g_dg = make_geom(2, P->Dp, P->Hp, P->Wp, halo_d, N);
   // wgrad: forward geometry, 32-cout groups
   P->g_wg = make_geom(2, P->Do, P->Ho, P->Wo, halo_f, N, 64);
-  static const int use_c1 = env_int("MI_CONV_C1", 1);
+  static const int use_c1 = mi_env_int("MI_CONV_C1", 1);
   auto c_ok = [](int c) { return c >= 8 && c <= 64 && (c & 7) == 0; };
   P->c1_in = use_c1 && P->full27 && Cin == 1 && c_ok(Cout);
   P->c1_out = use_c1 && P->full27 && Cout == 1 && c_ok(Cin);
-  static const int use27 = env_int("MI_CONV27", 1);  // 0: keep every conv on the table-driven kernel (A/B runs)
+  static const int use27 = mi_env_int("MI_CONV27", 1);  // 0: keep every conv on the table-driven kernel (A/B runs)
   const bool geo27 = P->full27 && P->g_fwd.TD == 4 && P->g_fwd.TH == 8 && P->g_fwd.TW == 8;
   P->v27_fwd = use27 && geo27 && (Cin % 8) == 0 && (Cout % 8) == 0;  // whole channel octets on both sides (else: table-driven kernel)
   P->v27_dg = use27 && geo27 && (Cout % 8) == 0 && (Cin % 8) == 0;
-  static const int use11 = env_int("MI_CONV1X1", 1);
+  static const int use11 = mi_env_int("MI_CONV1X1", 1);
   const bool k1 = P->KT == 1 && !P->strided;
   auto chunks_ok = [](int c) { int n = (c + 31) / 32; return n == 1 || n == 2 || n == 3 || n == 4 || n == 6; };
   P->v11_fwd = use11 && k1 && (Cin % 8) == 0 && chunks_ok(Cin) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
   P->v11_dg = use11 && k1 && (Cout % 8) == 0 && chunks_ok(Cout) && ((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 <= 96;
-  static const int use_g11 = env_int("MI_CONV1X1_GEMM", 1);  // 0: the table-driven kernel for those layers (A/B runs)
+  static const int use_g11 = mi_env_int("MI_CONV1X1_GEMM", 1);  // 0: the table-driven kernel for those layers (A/B runs)
   P->g11 = use_g11 && k1 && (!P->v11_fwd || !P->v11_dg) && (Cin % 8) == 0 && (Cout % 8) == 0;
   if (P->c1_in || P->c1_out) {
     const int C = P->c1_in ? Cout : Cin;
@@ -2487,13 +2465,10 @@ int conv_plan_wgrad_slabs(mi_conv_plan* P) {
   P->wg_nitems = (int)(off / 1024);
   const int ntiles = P->N * P->g_wg.tilesD * P->g_wg.tilesH * P->g_wg.tilesW;
   // + 6 tile times per workgroup: prologue, accumulator flush and the slab it adds to the reduce (three rounds of 32 tiles measured 383 us
-  // against ~305 for one round of 103).  Optionally + the slab round trip: every split writes its slab and the reduce kernel reads it back;
-  // MI_WGRAD_SLAB_COST = hundredths of a tile time per MB and split -- 2 x 1 MB / 3 TB/s = 0.67 us = ~22; measured: no setting moves the step
-  static const int slab_cost = env_int("MI_WGRAD_SLAB_COST", 0);
-  int nsplit = pick_nsplit(ntiles, npairs, 6, (int64_t)slab_cost * (off * 4 / (1 << 20)));
-  static const int old_split = env_int("MI_WGRAD_SPLIT_OLD", 0);  // A/B knob: the round-1 choice
-  if (old_split) nsplit = (256 + npairs - 1) / npairs;
-  static const int force_split = env_int("MI_WGRAD_NSPLIT", 0);  // probe knob: this many splits for every layer of at most 64 tiles
+  // against ~305 for one round of 103).  The slab round trip (every split writes its slab and the reduce kernel reads it back) is not priced in:
+  // at 2 x 1 MB / 3 TB/s = 0.67 us = ~0.22 tile times per MB and split, measured: no setting moves the step
+  int nsplit = pick_nsplit(ntiles, npairs, 6);
+  static const int force_split = mi_env_int("MI_WGRAD_NSPLIT", 0);  // probe knob: this many splits for every layer of at most 64 tiles
   if (force_split && ntiles <= 64) nsplit = force_split;
   if (nsplit > ntiles) nsplit = ntiles;
   while (nsplit > 1 && (int64_t)nsplit * off * 4 > (256ll << 20)) nsplit /= 2;  // cap the slab at 256 MiB
@@ -2509,7 +2484,7 @@ int conv_plan_wgrad_slabs(mi_conv_plan* P) {
 // Both directions of a factor-2 layer on the phase kernels, or neither: channel counts or a geometry they do not serve (UNSUPPORTED) leave
 // the plan on its other routes.  gd, gh, gw: the coarse grid.
 int phase_sides_create(mi_conv_plan* P, PhaseKind kind_fwd, int mode_fwd, PhaseKind kind_dg, int mode_dg, int gd, int gh, int gw) {
-  static const int use_ph = env_int("MI_CONVPH", 1);
+  static const int use_ph = mi_env_int("MI_CONVPH", 1);
   if (!use_ph || (P->Cin % 8) != 0 || (P->Cout % 8) != 0) return 0;
   int e = phase_side_create(P->ph_fwd, kind_fwd, mode_fwd, 0, P->Cout, P->Cin, gd, gh, gw, P->N);
   if (!e) e = phase_side_create(P->ph_dg, kind_dg, mode_dg, 1, P->Cin, P->Cout, gd, gh, gw, P->N);
@@ -2754,7 +2729,7 @@ int mi_conv_pack_batch_create(mi_pack_batch** out, mi_conv_plan* const* plans, c
   int g11_nblocks = 0;
   std::vector<PackSuper> supers;
   size_t lds_super = 0;
-  static const int use_super = env_int("MI_PACK_SUPER", 1);  // 0: one block per group, every weight read once per table (A/B runs)
+  static const int use_super = mi_env_int("MI_PACK_SUPER", 1);  // 0: one block per group, every weight read once per table (A/B runs)
   bool super_ok = use_super != 0;
   for (int i = 0; i < n; ++i) {
     mi_conv_plan* P = plans[i];
@@ -2805,7 +2780,6 @@ int mi_conv_pack_batch_create(mi_pack_batch** out, mi_conv_plan* const* plans, c
   B->ngroups = (int)groups.size(); B->lds = lds;
   B->nphase = (int)phase.size(); B->phase_blocks = phase_blocks;
   B->ng11 = (int)g11.size(); B->g11_blocks = g11_nblocks;
-  if (use_super > 1) fprintf(stderr, "[pack batch] %d plans, %zu groups, %zu super-groups, paired: %d, LDS %zu B\n", n, groups.size(), supers.size(), (int)super_ok, lds_super);
   if (super_ok && !supers.empty() && lds_super <= 150 * 1024) {
     bool lds_raised = false;  // (per batch, as before the helper)
     if (hipMalloc((void**)&B->d_supers, sizeof(PackSuper) * supers.size()) != hipSuccess ||
@@ -3009,7 +2983,7 @@ static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const float* sca
   memset(&w, 0, sizeof(w));
   ConvArgs& a = w.c;
   const Geom& g = P->g_wg;
-  static const int use_w2 = env_int("MI_WGRAD2", 1);
+  static const int use_w2 = mi_env_int("MI_WGRAD2", 1);
   const int nvox = g.TD * g.TH * g.TW, px = (g.lds_bytes + 1023) / 1024, py = (nvox * 64 + 1023) / 1024;
   const unsigned dyb = span32(P->N, P->Do, P->Ho, P->Wo, dy_cs);
   const bool dma_ok = use_w2 && !scale_shift && g.vox == 64 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && px <= 40 && py <= 16 && dyb;
@@ -3034,7 +3008,7 @@ static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const float* sca
   w.contig = wgrad_contig(w.ntiles, w.nsplit);
   static const int dbg = mi_diag_knob("MI_WGRAD_DBG"); w.dbg = dbg;
   w.colsum = dy_colsum; w.colsum_stride = dy_colsum_stride;
-  static const int cs_slab = env_int("MI_CS_SLAB", 1);
+  static const int cs_slab = mi_env_int("MI_CS_SLAB", 1);
   bool cs_pairs_multi_tap = true;  // pairs that own the column sums (first chunk of a cout block) must be tap pairs, not k-split pairs
   for (int yy = 0; yy < P->wg.ny; ++yy) cs_pairs_multi_tap = cs_pairs_multi_tap && P->wg.hdr[((size_t)yy * P->wg.nchunks) * 4 + 1] > 1;
   w.cs_part = (cs_slab && dy_colsum && cs_pairs_multi_tap) ? P->d_cspart : nullptr;
@@ -3051,12 +3025,12 @@ static int launch_wgrad_dma(const mi_conv_plan* P, WgradArgs& w, bool direct, hi
   const Geom& g = w.c.g;
   const int px = (g.lds_bytes + 1023) / 1024, py = (g.TD * g.TH * g.TW * 64 + 1023) / 1024;
   w.nbuf = (P->KT == 1 && px == 16 && py == 16) ? 4 : 2;  // 1x1: tiles are pure loads -> three tiles in flight per workgroup
-  static const int use_flags = env_int("MI_WGRAD_FLAGS", 1); w.flags = use_flags;
+  static const int use_flags = mi_env_int("MI_WGRAD_FLAGS", 1); w.flags = use_flags;
   const size_t lds2 = (size_t)(w.nbuf * (px + py)) * 1024 + 64;  // + the hand-off counters
   const bool geo3 = P->full27 && g.row == WG3_XROW && g.slice == WG3_XSLICE && g.TD == 4 && g.TH == 8 && g.TW == 8;
   static bool raised3 = false, raisedg = false, raisedr = false;
   if (int e = geo3 ? raise_lds_limit((const void*)k_conv_wgrad2<true>, raised3) : raise_lds_limit((const void*)k_conv_wgrad2<false>, raisedg)) return e;
-  static const int use_roll = env_int("MI_WGRAD_ROLL", 1);  // 0: k_conv_wgrad2 for every layer (A/B runs)
+  static const int use_roll = mi_env_int("MI_WGRAD_ROLL", 1);  // 0: k_conv_wgrad2 for every layer (A/B runs)
   // (runs of more than two columns lose more to L2 locality -- the workgroups of an XCD are then columns apart -- than the saved
   // pieces return: 64->64 and 96->32 at 128^3 measured +1 / +2.5 %, 32->32 -6 %, 64->32 -3.5 %, the 64^3 .. 16^3 levels -1.5 .. -3 %)
   const bool roll = use_roll && geo3 && !direct && w.sx == 1 && w.sy == 1 && w.nbuf == 2 && w.flags && P->wg.hdr[1] == 27 && w.nsplit <= w.ntiles &&
@@ -3104,12 +3078,12 @@ int mi_conv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const float* scale_s
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
   if (P->up) return wgrad_upconv_fallback(P, x, x_cs, scale_shift, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
-  static const int use_w11 = env_int("MI_WGRAD1X1", 1);
+  static const int use_w11 = mi_env_int("MI_WGRAD1X1", 1);
   if (use_w11 && P->KT == 1 && !P->strided && !scale_shift && !(dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout)) {
     const int e = mi_launch_wgrad1x1(x, x_cs, P->Cin, dy, dy_cs, P->Cout, P->N, (int64_t)P->Di * P->Hi * P->Wi, dw, dy_colsum, dy_colsum_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  static const int use_c1w = env_int("MI_C1_WGRAD", 1);
+  static const int use_c1w = mi_env_int("MI_C1_WGRAD", 1);
   if (use_c1w && (P->c1_in || P->c1_out) && P->d_c1part && !scale_shift && !(dy_colsum && dy_colsum_stride != 0)) {
     // one channel on one side: a streaming kernel with the 27 taps as the GEMM's N axis (conv_c1.hip) instead of padding that side to 32
     const int e = P->c1_in ? mi_launch_c1_wgrad(dy, dy_cs, x, x_cs, dw, dy_colsum, nullptr, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st)

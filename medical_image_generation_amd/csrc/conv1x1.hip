@@ -101,9 +101,8 @@ template <int NCH>
 int launch11(const ConvArgs& a, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vpi, hipStream_t st) {
   size_t lds = (size_t)nfrags * 1024;
   // staged stores (see the kernel): whole channel octets, 16-byte aligned pitch, a tile per wave that fits beside the weights
-  static const char* stage_env = getenv("MI_C11_STAGE");
   const size_t tile_bytes = (size_t)4 * 32 * (a.Cout * 2 + 16);
-  const int stage = (!stage_env || atoi(stage_env)) && (a.y_cs & 7) == 0 && (a.Cout & 7) == 0 && a.y_bytes != 0 && a.Cout >= 16 && lds + tile_bytes <= 64 * 1024;
+  const int stage = (a.y_cs & 7) == 0 && (a.Cout & 7) == 0 && a.y_bytes != 0 && a.Cout >= 16 && lds + tile_bytes <= 64 * 1024;
   if (stage) lds += tile_bytes;
   auto kern = k_conv1x1<NCH>;
   static bool attr_set = false;
@@ -433,10 +432,9 @@ int launch_w11(const W11Args& p, int gy, int gz, hipStream_t st) {
   }
   const int64_t ntiles = (p.nvox + 255) / 256;
   // splits over the voxel tiles: every split ends in (NCO * NCI * 1024) float atomics per workgroup, so wide layers (many channel pairs)
-  // want few of them.  MI_W11_MIN_SPLIT / MI_W11_WGS: A/B knobs
+  // want few of them: ~512 workgroups in all, at least 4 splits
   // (32 / 512 until late in round 3; 4: C3b 58.0 -> 57.2 ms, C5 48.3 -> 47.5, C4 21.51 -> 21.44, profiles/r04a_ab_w11_split*.log)
-  static const int min_split = [] { const char* e = getenv("MI_W11_MIN_SPLIT"); return e && atoi(e) > 0 ? atoi(e) : 4; }();
-  static const int want_wgs = [] { const char* e = getenv("MI_W11_WGS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();
+  const int min_split = 4, want_wgs = 512;
   int gx = want_wgs / (gy * gz);
   if (gx < min_split) gx = min_split;
   if (gx > ntiles) gx = (int)ntiles;
@@ -456,9 +454,9 @@ int mi_launch_wgrad1x1(const void* x, int x_cs, int Cin, const void* dy, int dy_
   p.x = (const bf16*)x; p.x_cs = x_cs; p.Cin = Cin; p.dy = (const bf16*)dy; p.dy_cs = dy_cs; p.Cout = Cout;
   p.dw = dw; p.colsum = colsum; p.colsum_stride = colsum_stride; p.nvox = (int64_t)N * V; p.vox_per_image = V;
   p.ci0 = 0; p.co0 = 0;
-  {  // wide layers: 128 x 128 workgroup blocks (k_wgrad1x1_wide); MI_W11_WIDE_MIN: smallest channel count that takes it (0: never)
-    static const int wide_min = [] { const char* e = getenv("MI_W11_WIDE_MIN"); return e ? atoi(e) : 256; }();
-    if (wide_min > 0 && Cin >= wide_min && Cout >= wide_min && Cin % 128 == 0 && Cout % 128 == 0 && (!colsum || colsum_stride == 0)) {
+  {  // wide layers: 128 x 128 workgroup blocks (k_wgrad1x1_wide); wide_min: smallest channel count that takes it
+    const int wide_min = 256;
+    if (Cin >= wide_min && Cout >= wide_min && Cin % 128 == 0 && Cout % 128 == 0 && (!colsum || colsum_stride == 0)) {
       static bool attr_set = false;
       if (!attr_set) {
         hipError_t e = hipFuncSetAttribute((const void*)k_wgrad1x1_wide, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -467,7 +465,7 @@ int mi_launch_wgrad1x1(const void* x, int x_cs, int Cin, const void* dy, int dy_
       }
       const int gy = Cin / 128, gz = Cout / 128;
       const int64_t ntiles = (p.nvox + 255) / 256;
-      static const int wide_wgs = [] { const char* e = getenv("MI_W11_WIDE_WGS"); return e && atoi(e) > 0 ? atoi(e) : 256; }();
+      const int wide_wgs = 256;  // ~ workgroups in all
       int gx = wide_wgs / (gy * gz);
       if (gx < 1) gx = 1;
       if (gx > ntiles) gx = (int)ntiles;

@@ -42,13 +42,16 @@ template <int FLIP>
 __global__ void __launch_bounds__(512, 2) k_conv27r(ConvArgs a) {
   conv27r_body<FLIP>(a);
 }
+inline int c27_dbg() {  // (one read for every instance of the two launch templates)
+  static const int dbg = mi_diag_knob("MI_C27_DBG");
+  return dbg;
+}
 // single-chunk 32-channel layers with at least a few tiles per column: the rolling-halo variant (conv27_kernel.h, MODE 3)
 template <int FLIP>
 int launch27r(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   using KK = K<1, 3>;
   a.ntiles = ntiles;
-  static const int dbg = mi_diag_knob("MI_C27_DBG");
-  a.dbg = dbg & ~64;
+  a.dbg = c27_dbg() & ~64;
   const int gx = mi_conv27_grid_x(ntiles, ny);
   if (a.stats && a.stats_chunks != 4 * gx) return MI_ERR_BAD_ARG;
   auto kern = k_conv27r<FLIP>;
@@ -68,8 +71,7 @@ template <int NCB, int FLIP>
 int launch27(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   using KK = K<NCB, 0>;
   a.ntiles = ntiles;
-  static const int dbg = mi_diag_knob("MI_C27_DBG");
-  a.dbg = dbg;
+  a.dbg = c27_dbg();
   const int gx = mi_conv27_grid_x(ntiles, ny);
   if (a.stats && a.stats_chunks != 4 * gx) return MI_ERR_BAD_ARG;
   auto kern = k_conv27<NCB, FLIP>;
@@ -109,7 +111,7 @@ int mi_launch_conv27(const ConvArgs& a, int NCB, int flip, int ntiles, int ny, h
   if (a.g.TD != 4 || a.g.TH != 8 || a.g.TW != 8 || (a.x_cs & 7) || (a.Cin & 7)) return MI_ERR_BAD_ARG;
   if ((a.y_cs & 7) || (a.Cout & 7) || a.y_bytes == 0) return MI_ERR_UNSUPPORTED;  // whole 16-byte pieces only (the caller falls back)
   if (a.res && (a.res_bytes == 0 || (a.res_cs & 7))) return MI_ERR_UNSUPPORTED;  // (>= 4 GiB is not reachable with the x_bytes limit)
-  static const int use_roll = [] { const char* e = getenv("MI_C27_ROLL"); return e ? atoi(e) : 1; }();  // 0: the plain kernel (A/B runs)
+  static const int use_roll = mi_env_int("MI_C27_ROLL", 1);  // 0: the plain kernel (A/B runs)
   if (NCB == 1 && a.nchunks == 1 && use_roll && a.g.tilesD >= 4 && a.Cin >= 32)
     return flip ? launch27r<1>(a, ntiles, ny, st) : launch27r<0>(a, ntiles, ny, st);
   if (NCB == 1) return flip ? launch27<1, 1>(a, ntiles, ny, st) : launch27<1, 0>(a, ntiles, ny, st);

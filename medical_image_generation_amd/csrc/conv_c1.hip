@@ -1,7 +1,7 @@
 // 3x3x3 stride-1 pad-1 convolutions with ONE channel on one side: the network's input conv (1 -> C, UNet:1820-1828, AEKL:393) and
 // output conv (C -> 1, UNet:1935-1943, AEKL:609).  On the implicit-GEMM kernels one side of the GEMM is padded from 1 to 32, so
 // 31/32 of the MFMA and LDS work is zeros (0.2 ms per call at 128^3 for 3.6 GFLOP); these are plain streaming kernels instead:
-//   k_c1_expand  : y[v][c]  = a[c] + sum_t s[v + t] W[c][t]          forward of 1 -> C, and data gradient of C -> 1 (taps flipped)
+//   k_c1_expand_mfma : y[v][c] = a[c] + sum_t s[v + t] W[c][t]       forward of 1 -> C, and data gradient of C -> 1 (taps flipped)
 //   k_c1_reduce  : y[v]     = a    + sum_t sum_c x[v + t][c] W[c][t]  forward of C -> 1:  Y[u][t] = x[u][:] . W[:][t] on the MFMA for
 //                                                                    the tile + halo, then 27 shifted LDS reads per output voxel
 //   k_c1_wgrad   : dW[c][t] += sum_v m[v][c] s[v +- t]   weight gradient of both (m = the C-channel tensor, s = the single-channel one):
@@ -34,65 +34,13 @@ struct C1Args {
   int stats_chunks;
 };
 
-// ---------------------------------------------------------------------------------------------- 1 -> C (and dgrad of C -> 1)
-// Thread = voxel (its 27 neighbours live in registers, weights come through the scalar cache).  Neighbour loads are UNCONDITIONAL on
-// clamped coordinates and masked afterwards: a predicated load per tap becomes 27 dependent branch + wait sequences.  The wave's
-// 64 voxels x C channels go through a wave-private LDS tile so that the global stores are contiguous 16-byte pieces.
-constexpr int kExpPitch = 64 * 2 + 16;  // bytes per voxel row of the staging tile (C <= 64)
-template <int FLIP>
-__global__ void __launch_bounds__(256) k_c1_expand(C1Args a) {
-  __shared__ __attribute__((aligned(16))) char stage[4][64 * kExpPitch];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t total = (int64_t)a.N * a.D * a.H * a.W;
-  const int64_t v0 = blockIdx.x * 256ll + wave * 64;  // first voxel of this wave
-  if (v0 >= total) return;
-  const int64_t v = v0 + lane < total ? v0 + lane : total - 1;
-  const int wx = (int)(v % a.W);
-  int64_t t1 = v / a.W;
-  const int hy = (int)(t1 % a.H);
-  t1 /= a.H;
-  const int dz = (int)(t1 % a.D), n = (int)(t1 / a.D);
-  const bf16* sn = a.s + (int64_t)n * a.D * a.H * a.W * a.s_cs;
-  float xs[27];
-#pragma unroll
-  for (int kd = 0; kd < 3; ++kd)
-#pragma unroll
-    for (int kh = 0; kh < 3; ++kh)
-#pragma unroll
-      for (int kw = 0; kw < 3; ++kw) {
-        const int z = dz + kd - 1, yy = hy + kh - 1, x = wx + kw - 1;
-        const int zc = min(max(z, 0), a.D - 1), yc = min(max(yy, 0), a.H - 1), xc = min(max(x, 0), a.W - 1);
-        const float val = bf2f(sn[(((int64_t)zc * a.H + yc) * a.W + xc) * a.s_cs]);
-        xs[(kd * 3 + kh) * 3 + kw] = (z == zc && yy == yc && x == xc) ? val : 0.f;
-      }
-  char* my = stage[wave];
-  for (int c0 = 0; c0 < a.C; c0 += 8) {
-    F8 acc;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc.v[j] = a.addvec ? a.addvec[(int64_t)n * a.av_stride + c0 + j] : 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float* wr = a.w + (c0 + j) * 27;  // uniform address: scalar loads
-#pragma unroll
-      for (int t = 0; t < 27; ++t) acc.v[j] = fmaf(xs[t], wr[FLIP ? 26 - t : t], acc.v[j]);
-    }
-    *(u32x4*)(my + lane * kExpPitch + c0 * 2) = pack8(acc);
-  }
-  // (wave-private tile: LDS operations of one wave complete in order, no barrier needed)
-  const int C8 = a.C / 8;
-  for (int i = lane; i < 64 * C8; i += 64) {
-    const int vox = i / C8, ch = i % C8;
-    if (v0 + vox < total) *(u32x4*)(a.y + (v0 + vox) * a.y_cs + ch * 8) = *(const u32x4*)(my + vox * kExpPitch + ch * 16);
-  }
-}
-
-// ---------------------------------------------------------------------------------------------- 1 -> C on the MFMA
-// The same product with the 27 taps as the K axis: D[c][v] = W[c][t] B[t][v], B[t][v] = s[v + t] gathered from a wave-private LDS
+// ---------------------------------------------------------------------------------------------- 1 -> C (and dgrad of C -> 1) on the MFMA
+// The 27 taps are the K axis: D[c][v] = W[c][t] B[t][v], B[t][v] = s[v + t] gathered from a wave-private LDS
 // halo (3 slices x 10 x 10) of the single-channel tensor; two k-steps of 16 taps (27 padded to 32) per block of 32 voxels.  The
 // weight rows are permuted like k_conv27's (MFMA row rho <-> channel 16 ((rho >> 2) & 1) + (rho & 3) + 4 (rho >> 3)) so that a
 // lane's 16 accumulator registers are 16 CONSECUTIVE channels of its voxel: the result is stored straight from the registers as
-// two 16-byte pieces per lane, no staging tile, no 864-FMA VALU loop.  One HBM write pass (the VALU kernel above: 86 us at 128^3
-// for a 134 MB write).
+// two 16-byte pieces per lane, no staging tile, no 864-FMA VALU loop.  One HBM write pass (the thread-per-voxel VALU kernel this
+// replaced: 86 us at 128^3 for a 134 MB write).
 constexpr int kTD = 4, kTH = 8, kTW = 8, kHD = kTD + 2, kHH = kTH + 2, kHW = kTW + 2, kHalo = kHD * kHH * kHW;  // 600 halo voxels
 template <int NCB, int FLIP>
 __global__ void __launch_bounds__(256) k_c1_expand_mfma(C1Args a, int ntiles) {
@@ -466,14 +414,10 @@ bool c1_dims_ok(int N, int D, int H, int W, int C) {
 
 }  // namespace
 
-static int c1_use_mfma() {
-  static const int v = [] { const char* e = getenv("MI_C1_EXPAND_MFMA"); return e ? atoi(e) : 1; }();
-  return v;
-}
 // chunks of the statistics the 1 -> C forward emits (0: this shape does not emit them)
 int mi_c1_expand_stats_chunks(int N, int D, int H, int W, int C) {
-  static const int on = [] { const char* e = getenv("MI_C1_STATS"); return e ? atoi(e) : 1; }();  // 0: separate statistics pass (A/B runs)
-  if (!on || !c1_use_mfma() || !c1_dims_ok(N, D, H, W, C) || C > 32 || N > 16) return 0;
+  static const int on = mi_env_int("MI_C1_STATS", 1);  // 0: separate statistics pass (A/B runs)
+  if (!on || !c1_dims_ok(N, D, H, W, C) || C > 32 || N > 16) return 0;
   const int64_t tiles = (int64_t)N * ((D + kTD - 1) / kTD) * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW);
   if (tiles >= (1ll << 31)) return 0;
   return (int)(tiles < 2048 ? tiles : 2048);
@@ -486,25 +430,17 @@ int mi_launch_c1_expand(const void* s, int s_cs, const float* w, const float* ad
   a.s = (const bf16*)s; a.s_cs = s_cs; a.w = w; a.addvec = addvec; a.av_stride = av_stride; a.y = (bf16*)y; a.y_cs = y_cs;
   a.stats = stats; a.stats_chunks = stats ? mi_c1_expand_stats_chunks(N, D, H, W, C) : 0;
   if (stats && (flip || a.stats_chunks == 0)) return MI_ERR_UNSUPPORTED;
-  const int use_mfma = c1_use_mfma();
   const int64_t tiles = (int64_t)N * ((D + kTD - 1) / kTD) * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW);
-  if (use_mfma && tiles < (1ll << 31)) {
-    const int grid = (int)(tiles < 2048 ? tiles : 2048);  // persistent: 8 workgroups of 4 waves per CU
-    const int ncb = (C + 31) / 32;
-    if (ncb == 1) {
-      if (flip) hipLaunchKernelGGL((k_c1_expand_mfma<1, 1>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
-      else hipLaunchKernelGGL((k_c1_expand_mfma<1, 0>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
-    } else {
-      if (flip) hipLaunchKernelGGL((k_c1_expand_mfma<2, 1>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
-      else hipLaunchKernelGGL((k_c1_expand_mfma<2, 0>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
-    }
-    MI_CHECK_LAUNCH();
-    return 0;
+  if (tiles >= (1ll << 31)) return MI_ERR_UNSUPPORTED;
+  const int grid = (int)(tiles < 2048 ? tiles : 2048);  // persistent: 8 workgroups of 4 waves per CU
+  const int ncb = (C + 31) / 32;
+  if (ncb == 1) {
+    if (flip) hipLaunchKernelGGL((k_c1_expand_mfma<1, 1>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
+    else hipLaunchKernelGGL((k_c1_expand_mfma<1, 0>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
+  } else {
+    if (flip) hipLaunchKernelGGL((k_c1_expand_mfma<2, 1>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
+    else hipLaunchKernelGGL((k_c1_expand_mfma<2, 0>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
   }
-  const int64_t total = (int64_t)N * D * H * W;
-  dim3 grid((unsigned)((total + 255) / 256));
-  if (flip) hipLaunchKernelGGL(k_c1_expand<1>, grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL(k_c1_expand<0>, grid, dim3(256), 0, st, a);
   MI_CHECK_LAUNCH();
   return 0;
 }

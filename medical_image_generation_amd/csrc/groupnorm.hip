@@ -466,7 +466,7 @@ __global__ void __launch_bounds__(kT) k_gn_bwd_apply(const bf16* __restrict__ g,
 // total = 16-byte pieces of ONE image
 inline int64_t apply_grid(int64_t total, int C8, int N) {
   int64_t grid = (total + kT - 1) / kT;
-  static const int per_cu = [] { const char* e = getenv("MI_GN_BLOCKS_PER_CU"); return e && atoi(e) > 0 ? atoi(e) : 16; }();  // A/B knob
+  const int per_cu = 16;  // blocks per CU in all
   const int64_t cap = 256 * per_cu / N > 64 ? 256 * per_cu / N : 64;
   if (grid > cap) grid = cap;
   int m = C8;  // kT * grid % C8 == 0  <=>  grid % (C8 / gcd(C8, kT)) == 0
@@ -477,23 +477,19 @@ inline int64_t apply_grid(int64_t total, int C8, int N) {
 }
 
 inline int64_t pick_vchunk(int64_t V) {
-  // ~1024 blocks whatever the volume: a 16^3 x 256-channel tensor cut into 2048-voxel chunks would be streamed by 2 CUs
-  static const int nchunks = [] { const char* e = getenv("MI_GN_CHUNKS"); return e && atoi(e) > 0 ? atoi(e) : 512; }();  // A/B knobs
-  static const int nchunks_big = [] { const char* e = getenv("MI_GN_CHUNKS_BIG"); return e && atoi(e) > 0 ? atoi(e) : 0; }();
-  const int nc = (nchunks_big && V >= (1 << 20)) ? nchunks_big : nchunks;
+  // 512 chunks per image whatever the volume (EXPERIMENTS.md, round 3: 512 against 1024): a 16^3 x 256-channel tensor cut into
+  // 2048-voxel chunks would be streamed by 2 CUs
+  const int nc = 512;
   int64_t vc = (V + nc - 1) / nc;
   if (vc < 16) vc = 16;
   return vc;
 }
-// MI_GN_SWEEP (A/B knob, default 0 = every block walks its own chunk, both passes front to back).  Bit 0: the statistics passes sweep an
-// image front to back with all blocks abreast and the backward's apply pass walks it back to front, so that it meets the lines the
-// partial pass touched last while they could still be in the 256 MiB Infinity Cache; bit 1: the forward apply pass walks back to front
-// too.  Measured (round 3, profiles/r03b_ab_gn_sweep.log, same box, interleaved): 24.20 ms/step with 0, 24.25 with 1, 24.26 with 3;
-// mi_gn_bwd at 32 ch x 128^3 back to back: 139 us (0) vs 146 (1).  The two passes of a 268 MB working set gain nothing from the order.
-inline int gn_sweep() {
-  static const int v = [] { const char* e = getenv("MI_GN_SWEEP"); return e ? atoi(e) : 0; }();
-  return v;
-}
+// The kernels' sweep / reverse flag is always 0: every block walks its own chunk, both passes front to back.  With the flag set the
+// statistics passes sweep an image front to back with all blocks abreast and the apply passes walk it back to front, so that they meet
+// the lines the partial pass touched last while they could still be in the 256 MiB Infinity Cache.  Measured (round 3,
+// profiles/r03b_ab_gn_sweep.log, same box, interleaved): 24.20 ms/step without, 24.25 with the backward's passes swept, 24.26 with the
+// forward apply pass reversed too; mi_gn_bwd at 32 ch x 128^3 back to back: 139 us vs 146.  The two passes of a 268 MB working set gain
+// nothing from the order.
 inline bool bad_c(int C, int G) { return C <= 0 || (C & 7) || C > 2048 || G <= 0 || C % G != 0; }
 
 // ---- small tensors (the 16^3 level of the C4 net; 2-D nets): statistics -> coefficients -> apply in ONE launch.  Three launches of
@@ -610,7 +606,7 @@ int mi_gn_stats(const void* x, int x_cstride, int N, int64_t V, int C, int G, fl
   int chunks = (int)((V + vc - 1) / vc);
   int rows = kT / (C / 8);
   hipLaunchKernelGGL(k_gn_partial, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)x, x_cstride,
-                     (float*)workspace, C, V, vc, gn_sweep() & 1);
+                     (float*)workspace, C, V, vc, 0);
   hipLaunchKernelGGL(k_gn_finalize, dim3(N * G), dim3(256), 0, st, (const float*)workspace, chunks, C, (const float*)nullptr, 0, C, G, V, eps,
                      gamma, beta, scale_shift, mean_rstd);
   MI_CHECK_LAUNCH();
@@ -633,8 +629,7 @@ int mi_gn_apply(const void* x, int x_cstride, const float* scale_shift, void* y,
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
   if (silu < 0 || silu > 2) return MI_ERR_BAD_ARG;  // activation code: 0 none, 1 SiLU, 2 LeakyReLU(0.2)
   auto k = silu == 1 ? k_gn_apply<1> : (silu == 2 ? k_gn_apply<2> : k_gn_apply<0>);
-  hipLaunchKernelGGL(k, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)x, x_cstride, scale_shift, (bf16*)y, y_cstride, C / 8, V,
-                     gn_sweep() & 2 ? 1 : 0);
+  hipLaunchKernelGGL(k, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)x, x_cstride, scale_shift, (bf16*)y, y_cstride, C / 8, V, 0);
   MI_CHECK_LAUNCH();
   return 0;
 }
@@ -667,22 +662,18 @@ int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N,
   if (silu < 0 || silu > 2) return MI_ERR_BAD_ARG;
   auto kp = silu == 1 ? k_gn_bwd_partial<1> : (silu == 2 ? k_gn_bwd_partial<2> : k_gn_bwd_partial<0>);
   hipLaunchKernelGGL(kp, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)g, g_cstride, (const bf16*)x,
-                     x_cstride, scale_shift, (float*)workspace, C, V, vc, gn_sweep() & 1, (double*)nullptr, 1);
+                     x_cstride, scale_shift, (float*)workspace, C, V, vc, 0, (double*)nullptr, 1);
   hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(N * G), dim3(256), sizeof(float) * 2 * (size_t)(C / G), st, (const float*)workspace, chunks, C,
                      G, V, gamma, mean_rstd, coef, dgamma, dbeta);
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
-  // MI_GN_VARIANT (A/B; bit 0 = 4 pieces in flight per stream instead of 2, bit 1 = non-temporal loads of the streams this pass reads for
-  // the last time (g, the pending gradient branches) and non-temporal stores of dx).  Measured round 3, same box, interleaved
-  // (profiles/r03i_ab_gn_variant.log): 22.96 ms/step with 0, 23.03 with 1, 22.75 with 2 (the default), 22.87 with 3; mi_gn_bwd at
-  // 32 ch x 128^3 back to back 132.8 / 142.0 / 124.4 / 129.8 us.  The same hints on the forward apply pass and on the backward's partial
-  // pass measured within noise (profiles/r03i_ab_gn_nt2.log) and were not kept.
-  static const int variant = [] { const char* e = getenv("MI_GN_VARIANT"); return e ? atoi(e) : 2; }();
-  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, false> : (silu == 2 ? k_gn_bwd_apply<2, 2, false> : k_gn_bwd_apply<0, 2, false>);
-  if (variant == 1) ka = silu == 1 ? k_gn_bwd_apply<1, 4, false> : (silu == 2 ? k_gn_bwd_apply<2, 4, false> : k_gn_bwd_apply<0, 4, false>);
-  else if (variant == 2) ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
-  else if (variant == 3) ka = silu == 1 ? k_gn_bwd_apply<1, 4, true> : (silu == 2 ? k_gn_bwd_apply<2, 4, true> : k_gn_bwd_apply<0, 4, true>);
+  // k_gn_bwd_apply<ACT, 2, true>: 2 pieces in flight per stream, non-temporal loads of the streams this pass reads for the last time (g,
+  // the pending gradient branches) and non-temporal stores of dx.  Measured round 3, same box, interleaved
+  // (profiles/r03i_ab_gn_variant.log): 22.96 ms/step with <2, false>, 23.03 with <4, false>, 22.75 with <2, true>, 22.87 with <4, true>;
+  // mi_gn_bwd at 32 ch x 128^3 back to back 132.8 / 142.0 / 124.4 / 129.8 us.  The same hints on the forward apply pass and on the
+  // backward's partial pass measured within noise (profiles/r03i_ab_gn_nt2.log) and were not kept.
+  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
   hipLaunchKernelGGL(ka, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)g, g_cstride, (const bf16*)x, x_cstride, scale_shift, coef,
-                     (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride, C / 8, V, gn_sweep() & 1,
+                     (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride, C / 8, V, 0,
                      (const double*)nullptr, (const float*)nullptr, (const float*)nullptr, G, (float*)nullptr, (float*)nullptr, 1);
   MI_CHECK_LAUNCH();
   return 0;
@@ -699,18 +690,13 @@ int mi_gn_bwd_fused(const void* g, int g_cstride, const void* x, int x_cstride, 
   int rows = kT / (C / 8);
   if (silu < 0 || silu > 2) return MI_ERR_BAD_ARG;
   // replicas of the sums: one per 64 blocks of the partial pass, at most MI_GN_FUSED_REPLICAS (16; the caller's buffer is sized for that)
-  static const int rep_div = [] { const char* e = getenv("MI_GN_FUSED_REP_DIV"); return e && atoi(e) > 0 ? atoi(e) : 64; }();
-  int nrep = chunks / rep_div;
+  int nrep = chunks / 64;
   nrep = nrep < 1 ? 1 : (nrep > MI_GN_FUSED_REPLICAS ? MI_GN_FUSED_REPLICAS : nrep);
   auto kp = silu == 1 ? k_gn_bwd_partial<1> : (silu == 2 ? k_gn_bwd_partial<2> : k_gn_bwd_partial<0>);
   hipLaunchKernelGGL(kp, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)g, g_cstride, (const bf16*)x,
                      x_cstride, scale_shift, (float*)nullptr, C, V, vc, 0, sums_zeroed, nrep);
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
-  static const int variant = [] { const char* e = getenv("MI_GN_VARIANT"); return e ? atoi(e) : 2; }();
-  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, false> : (silu == 2 ? k_gn_bwd_apply<2, 2, false> : k_gn_bwd_apply<0, 2, false>);
-  if (variant == 1) ka = silu == 1 ? k_gn_bwd_apply<1, 4, false> : (silu == 2 ? k_gn_bwd_apply<2, 4, false> : k_gn_bwd_apply<0, 4, false>);
-  else if (variant == 2) ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
-  else if (variant == 3) ka = silu == 1 ? k_gn_bwd_apply<1, 4, true> : (silu == 2 ? k_gn_bwd_apply<2, 4, true> : k_gn_bwd_apply<0, 4, true>);
+  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
   hipLaunchKernelGGL(ka, dim3((int)grid, N), dim3(kT), sizeof(double) * 2 * (size_t)C, st, (const bf16*)g, g_cstride, (const bf16*)x, x_cstride,
                      scale_shift, (const float*)nullptr, (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride,
                      C / 8, V, 0, (const double*)sums_zeroed, gamma, mean_rstd, G, dgamma, dbeta, nrep);
