@@ -127,6 +127,49 @@ int mi_conv_dgrad(mi_conv_plan* plan, const void* dy, int dy_cstride, void* dx, 
  * batch into one row (= the bias gradient) */
 int mi_conv_wgrad(mi_conv_plan* plan, const void* x, int x_cstride, const float* scale_shift, int silu, const void* dy, int dy_cstride,
                   float* dweight, float* dy_colsum, int dy_colsum_stride, hipStream_t stream);
+/* Which kernel ran (tests): the id of the kernel family that the most recent mi_conv_fwd / mi_conv_dgrad / mi_conv_wgrad of the calling
+ * thread launched -- a host-side thread_local stored at each launch site, one value per instantiation family the dispatch can reach.
+ * An Upsample + conv plan on its fallback reports its inner plan's kernel.  Not a stream operation; nothing reads it on the hot path. */
+enum mi_conv_kernel {
+  MI_CK_NONE = 0,
+  MI_CK_PH_SCATTER_32 = 1,   /* convph.hip MODE 1, 32 / 64 output channels per workgroup */
+  MI_CK_PH_SCATTER_64 = 2,
+  MI_CK_PH_GATHER_32 = 3,    /* convph.hip MODE 2 */
+  MI_CK_PH_GATHER_64 = 4,
+  MI_CK_C27_1_FWD = 5,       /* conv27.hip k_conv27<1, 0>: 32 channels per workgroup */
+  MI_CK_C27_1_DG = 6,        /* ... <1, 1>: taps flipped */
+  MI_CK_C27_2_FWD = 7,       /* k_conv27<2, *>: 64 channels per workgroup */
+  MI_CK_C27_2_DG = 8,
+  MI_CK_C27_ROLL_FWD = 9,    /* k_conv27r: rolling halo */
+  MI_CK_C27_ROLL_DG = 10,
+  MI_CK_IGEMM_M0_32 = 11,    /* table-driven k_conv_igemm, MODE 0 (tap tables) */
+  MI_CK_IGEMM_M0_64 = 12,
+  MI_CK_IGEMM_M1_32 = 13,    /* MODE 1: k3 s1 forward */
+  MI_CK_IGEMM_M1_64 = 14,
+  MI_CK_IGEMM_M2_32 = 15,    /* MODE 2: k3 s1 data gradient */
+  MI_CK_IGEMM_M2_64 = 16,
+  MI_CK_1X1_STREAM = 17,     /* conv1x1.hip */
+  MI_CK_1X1_GEMM = 18,       /* 1x1 on mi_gemm_nt_bf16 */
+  MI_CK_C1_EXPAND = 19,      /* conv_c1.hip: 1 -> C (also the data gradient of C -> 1) */
+  MI_CK_C1_REDUCE = 20,      /* conv_c1.hip: C -> 1 */
+  MI_CK_WG_UP = 21,          /* weight gradients: k_wgrad_up (Upsample + conv phase pairs) */
+  MI_CK_WG_1X1 = 22,         /* k_wgrad1x1 / k_wgrad1x1_wide */
+  MI_CK_WG_C1 = 23,          /* k_c1_wgrad */
+  MI_CK_WG_ROLL = 24,        /* k_conv_wgrad3 */
+  MI_CK_WG2_GEO3 = 25,       /* k_conv_wgrad2<true> */
+  MI_CK_WG2_GEN = 26,        /* k_conv_wgrad2<false>, two buffers, x read through the plan's tables */
+  MI_CK_WG2_GEN_DIRECT = 27, /* ... k3 s2: class images gathered from x in place */
+  MI_CK_WG2_GEN_1X1 = 28,    /* ... the 4-buffer 1x1 form */
+  MI_CK_WG_REGS_GEO3 = 29,   /* register-staged k_conv_wgrad<5, 2, true> */
+  MI_CK_WG_REGS_NP2 = 30,    /* k_conv_wgrad<NP, 2, false> */
+  MI_CK_WG_REGS_NP3 = 31,
+  MI_CK_WG_REGS_NP5 = 32,
+  MI_CK_WG_REGS_NP8 = 33,
+  MI_CK_COUNT = 34
+};
+int mi_conv_last_kernel(void);
+/* number of splits of the tile range the plan's tiled weight-gradient kernels run with (the inner plan's on the Upsample fallback) */
+int mi_conv_plan_wgrad_splits(const mi_conv_plan* plan);
 /* out[n*out_stride + c] (+)= sum_v x[n][v][c]  (bias / time-embedding gradients) */
 /* Linear layers (AttentionBlock to_q / to_k / to_v, UNet:379-381; AEKL:240-242): weight and bias gradient in one pass over the
  * row-major bf16 activations: dw[out][in] (fp32, ACCUMULATED) += dy^T x, dbias[out] (optional, ACCUMULATED) += column sums of dy.

@@ -45,6 +45,8 @@ _SIGS = {
     "mi_conv_pack_batch_destroy": [_p],
     "mi_conv_fwd": [_p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p],
     "mi_conv_fwd_stats_chunks": [_p],
+    "mi_conv_last_kernel": [],
+    "mi_conv_plan_wgrad_splits": [_p],
     "mi_conv_dgrad": [_p, _p, _i, _p, _i, _p],
     "mi_conv_wgrad": [_p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p],
     "mi_linear_wgrad_bf16": [_p, _i, _i, _p, _i, _i, _l, _p, _p, _p],
@@ -132,13 +134,13 @@ _SIGS = {
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l}
 _NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
-            "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits"}
+            "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits"}
 
 _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 15
+ABI_VERSION = 16
 
 
 def exported_symbols() -> list[str]:

@@ -396,11 +396,11 @@ __global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
             for (int i = 0; i < 4; ++i)
               if (co + i < cls_lim) v[i] += av[i];
           }
-          if (a.res) {
+          if (a.res) {  // conv + addvec is rounded to bf16 once, the residual is added to that and rounded again: the two roundings of conv27.hip
             const bf16* rp = a.res + vox * a.res_cs + co;
 #pragma unroll
             for (int i = 0; i < 4; ++i)
-              if (co + i < cls_lim) v[i] += bf2f(rp[i]);
+              if (co + i < cls_lim) v[i] = bf2f(f2bf(v[i])) + bf2f(rp[i]);
           }
           bf16* yp = a.y + vox * a.y_cs + co;
           if (full) {
@@ -1253,9 +1253,13 @@ __global__ void __launch_bounds__(768, 3) k_conv_wgrad3(WgradArgs w) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   typedef __attribute__((address_space(3))) char lds_char;
   const unsigned lds_base = (unsigned)(size_t)(lds_char*)lds;
-  unsigned* const fl_ready = (unsigned*)(lds + WR_XRING + 2 * WR_YB);  // tiles landed (x 4 loader waves); [1]: tiles left (x 8 compute waves)
-  unsigned* const fl_freed = fl_ready + 1;
-  if (threadIdx.x < 2) fl_ready[threadIdx.x] = 0u;  // (ordered before any use by the prologue barrier)
+  // Hand-off counters, one per PARITY of the tile's number in the run: fl_ready[p] tiles landed (x 4 loader waves), fl_freed[p] tiles left
+  // (x 8 compute waves).  One running count per direction is not enough: nothing keeps the waves of a group in step, so a loader wave that
+  // is a tile ahead would stand in for one whose pieces of the awaited tile are still in flight (and a compute wave that is a tile ahead
+  // for one still reading the tile being released).  A wave can lead its group by one tile at most, so two counters separate them.
+  unsigned* const fl_ready = (unsigned*)(lds + WR_XRING + 2 * WR_YB);
+  unsigned* const fl_freed = fl_ready + 2;
+  if (threadIdx.x < 4) fl_ready[threadIdx.x] = 0u;  // (ordered before any use by the prologue barrier)
   int pair, split;
   if (w.nsplit >= 8) {  // XCD-aware placement: see k_conv_wgrad
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
@@ -1314,16 +1318,17 @@ __global__ void __launch_bounds__(768, 3) k_conv_wgrad3(WgradArgs w) {
     flag_bump(fl_ready, lane);
     for (int t = t0 + 1; t < tend; ++t, ++it) {  // request tile t = number it+1 of the run while number it is being consumed
       const bool rolls = step_digits();
-      if (it > 0) flag_wait(fl_freed, 8u * (unsigned)it);  // tiles 0 .. it-1 have been left: group slot (G + 2) % 3 and dY buffer (it + 1) & 1 are free
+      // tile it-1 has been left by every compute wave (and with it all before): group slot (G + 2) % 3 and dY buffer (it + 1) & 1 are free
+      if (it > 0) flag_wait(fl_freed + ((it - 1) & 1), 8u * (unsigned)((it - 1) / 2 + 1));
       group((G + 2) % 3, rolls ? td * g.TD + 3 : td * g.TD - 1);
       dytile((it + 1) & 1);
       if (!rolls) {  // a new column: its second group goes where tile `it` still reads its first
-        flag_wait(fl_freed, 8u * (unsigned)(it + 1));
+        flag_wait(fl_freed + (it & 1), 8u * (unsigned)(it / 2 + 1));
         group(G % 3, td * g.TD + 3);
       }
       G += rolls ? 1 : 2;
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      flag_bump(fl_ready, lane);
+      flag_bump(fl_ready + ((it + 1) & 1), lane);
     }
     __builtin_amdgcn_s_barrier();  // every compute wave has finished its last tile
     return;
@@ -1381,7 +1386,7 @@ __global__ void __launch_bounds__(768, 3) k_conv_wgrad3(WgradArgs w) {
 #endif
   int G = 0, it = 0;
   for (int t = t0; t < tend; ++t, ++it) {
-    flag_wait(fl_ready, 4u * (unsigned)(it + 1));
+    flag_wait(fl_ready + (it & 1), 4u * (unsigned)(it / 2 + 1));
     if (cs_wave && n != cs_n) {
       cs_flush(cs_n);
       cs_n = n;
@@ -1395,7 +1400,7 @@ __global__ void __launch_bounds__(768, 3) k_conv_wgrad3(WgradArgs w) {
       else wg3_tile<3, false>(a3, t3, cs, lds0, ldy0, kh, q, chan_b);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of the tile have returned
-    flag_bump(fl_freed, lane);
+    flag_bump(fl_freed + (it & 1), lane);
     if (t + 1 < tend) G += step_digits() ? 1 : 2;
   }
   if (wave == 0) WG3_STAMP(3);
@@ -2029,6 +2034,10 @@ Geom make_geom(int VB, int Do, int Ho, int Wo, const int halo[3], int N, int vox
 
 }  // namespace
 
+// kernel family of the calling thread's most recent launch (enum mi_conv_kernel): written by the launch sites, read by mi_conv_last_kernel
+static thread_local int g_conv_last_kernel = MI_CK_NONE;
+void mi_conv_note_kernel(int id) { g_conv_last_kernel = id; }
+
 // One direction of a factor-2 layer on the phase kernels of convph.hip
 struct PhaseSide {
   int mode = 0;            // 1 scatter / 2 gather; 0: this direction does not run there
@@ -2236,6 +2245,9 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
     auto kern = k_conv_igemm<NCB, VB, NPV, RING, WPS, MODE>;                                               \
     static bool raised = false; /* one flag per instantiation */                                           \
     if (int e = raise_lds_limit((const void*)kern, raised)) return e;                                      \
+    mi_conv_note_kernel(MODE == 0 ? (NCB == 2 ? MI_CK_IGEMM_M0_64 : MI_CK_IGEMM_M0_32)                     \
+                        : MODE == 1 ? (NCB == 2 ? MI_CK_IGEMM_M1_64 : MI_CK_IGEMM_M1_32)                   \
+                                    : (NCB == 2 ? MI_CK_IGEMM_M2_64 : MI_CK_IGEMM_M2_32));                 \
     hipLaunchKernelGGL(kern, grid, blk, lds, st, a);                                                       \
   } while (0)
   if constexpr (MODE != 0) {  // fixed 4x8x8 (+halo) geometry: 2400 pieces -> 10 per thread
@@ -2385,6 +2397,7 @@ int upconv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int d
   const size_t lds = 2 * WGU_XSLOT + WGU_NBY * WGU_YSLOT + 64;
   static bool raised = false;
   if (int e = raise_lds_limit((const void*)k_wgrad_up, raised)) return e;
+  mi_conv_note_kernel(MI_CK_WG_UP);
   hipLaunchKernelGGL(k_wgrad_up, dim3(wgrad_grid(w.npairs, w.nsplit)), dim3(768), lds, st, w);
   CsReduce cs{w.cs_part, P->wg_nsplit * 8, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0};
   cs.nbx = (cs.Cout + 31) / 32;
@@ -2836,6 +2849,12 @@ int mi_conv_pack_batch_destroy(mi_pack_batch* B) {
   return 0;
 }
 
+int mi_conv_last_kernel(void) { return g_conv_last_kernel; }
+int mi_conv_plan_wgrad_splits(const mi_conv_plan* P) {
+  if (!P) return 0;
+  return P->up && !P->up_wg && P->up_inner ? P->up_inner->wg_nsplit : P->wg_nsplit;
+}
+
 int mi_conv_fwd_stats_chunks(const mi_conv_plan* P) {
   if (P && !P->up && P->c1_in) return mi_c1_expand_stats_chunks(P->N, P->Di, P->Hi, P->Wi, P->Cout);  // the network's input conv (conv_c1.hip)
   if (!P || P->up || !P->v27_fwd || P->N > 16 || P->ncb_fwd != 1) return 0;
@@ -2896,9 +2915,11 @@ int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shi
   int ntiles;
   if (int e = fwd_args(P, x, x_cs, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, a, ntiles, st)) return e;
   if (P->g11 && !P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0 && (y_cs & 7) == 0 && addvec_stride == 0 && !out_stats &&
-      ((uintptr_t)x & 15) == 0 && (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // 1x1 on the NT GEMM: y[vox][co] = x[vox][:] . W[co][:] + bias
+      ((uintptr_t)x & 15) == 0 && (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31)) {  // 1x1 on the NT GEMM: y[vox][co] = x[vox][:] . W[co][:] + bias
+    mi_conv_note_kernel(MI_CK_1X1_GEMM);
     return mi_gemm_nt_bf16(x, x_cs, 0, 0, P->d_w11, P->Cin, 0, 0, y, y_cs, 0, 0, addvec, nullptr, 0, 0, 0, P->N * P->Do * P->Ho * P->Wo, P->Cout, P->Cin, 1, 1,
                            1.0f, 0, 0, st);
+  }
   if (P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
     a.y_bytes = span32(P->N, P->Do, P->Ho, P->Wo, y_cs);  // (0: unbounded)
     return mi_launch_conv1x1(a, P->ncb_fwd, P->fwd.ny, st);
@@ -2949,9 +2970,11 @@ int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_c
   int ntiles;
   if (int e = dgrad_args(P, dy, dy_cs, dx, dx_cs, a, ntiles)) return e;
   if (P->g11 && !P->v11_dg && (dy_cs & 7) == 0 && (dx_cs & 7) == 0 && ((uintptr_t)dy & 15) == 0 &&
-      (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31))  // 1x1 on the NT GEMM: dx[vox][ci] = dy[vox][:] . W^T[ci][:]
+      (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31)) {  // 1x1 on the NT GEMM: dx[vox][ci] = dy[vox][:] . W^T[ci][:]
+    mi_conv_note_kernel(MI_CK_1X1_GEMM);
     return mi_gemm_nt_bf16(dy, dy_cs, 0, 0, P->d_w11t, P->Cout, 0, 0, dx, dx_cs, 0, 0, nullptr, nullptr, 0, 0, 0, P->N * P->Do * P->Ho * P->Wo, P->Cin, P->Cout, 1,
                            1, 1.0f, 0, 0, st);
+  }
   if (P->v11_dg && (dy_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
     a.y_bytes = span32(P->N, a.Do, a.Ho, a.Wo, a.y_cs);  // (0: unbounded)
     return mi_launch_conv1x1(a, P->ncb_dg, P->dg.ny, st);
@@ -3039,10 +3062,16 @@ static int launch_wgrad_dma(const mi_conv_plan* P, WgradArgs& w, bool direct, hi
   if (roll) {
     if (int e = raise_lds_limit((const void*)k_conv_wgrad3, raisedr)) return e;
     wg3_diag_arm();
+    mi_conv_note_kernel(MI_CK_WG_ROLL);
     hipLaunchKernelGGL(k_conv_wgrad3, grid, dim3(768), (size_t)WR_LDS, st, w);
     wg3_diag_report(P->Cin, P->Cout, w.ntiles, w.nsplit, grid.x);
-  } else if (geo3) hipLaunchKernelGGL(k_conv_wgrad2<true>, grid, dim3(768), lds2, st, w);
-  else hipLaunchKernelGGL(k_conv_wgrad2<false>, grid, dim3(768), lds2, st, w);
+  } else if (geo3) {
+    mi_conv_note_kernel(MI_CK_WG2_GEO3);
+    hipLaunchKernelGGL(k_conv_wgrad2<true>, grid, dim3(768), lds2, st, w);
+  } else {
+    mi_conv_note_kernel(direct ? MI_CK_WG2_GEN_DIRECT : w.nbuf == 4 ? MI_CK_WG2_GEN_1X1 : MI_CK_WG2_GEN);
+    hipLaunchKernelGGL(k_conv_wgrad2<false>, grid, dim3(768), lds2, st, w);
+  }
   wg2_diag_report();
   return 0;
 }
@@ -3056,6 +3085,7 @@ static int launch_wgrad_regs(const mi_conv_plan* P, const WgradArgs& w, hipStrea
     auto kern = k_conv_wgrad<NPV, 2, G3>;                                     \
     static bool raised = false;                                               \
     if (int e = raise_lds_limit((const void*)kern, raised)) return e;         \
+    mi_conv_note_kernel(G3 ? MI_CK_WG_REGS_GEO3 : NPV == 2 ? MI_CK_WG_REGS_NP2 : NPV == 3 ? MI_CK_WG_REGS_NP3 : NPV == 5 ? MI_CK_WG_REGS_NP5 : MI_CK_WG_REGS_NP8); \
     hipLaunchKernelGGL(kern, grid, blk, lds, st, w);                          \
   } while (0)
   const int np8 = (g.HD * g.HH * g.HW * 4 + 511) / 512;

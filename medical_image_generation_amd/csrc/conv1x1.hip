@@ -131,6 +131,7 @@ int mi_launch_conv1x1(const ConvArgs& a, int NCB, int ny, hipStream_t st) {
   if (nfrags * 1024 > 96 * 1024) return MI_ERR_UNSUPPORTED;
   const int64_t vpi = (int64_t)a.Do * a.Ho * a.Wo, nvox = vpi * a.N;
   const int ncb_total = (a.Cout + 31) / 32;
+  mi_conv_note_kernel(MI_CK_1X1_STREAM);
   switch (nch) {
     case 1: return launch11<1>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
     case 2: return launch11<2>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
@@ -450,6 +451,7 @@ int mi_launch_wgrad1x1(const void* x, int x_cs, int Cin, const void* dy, int dy_
                        int colsum_stride, hipStream_t st) {
   if ((x_cs & 7) || (dy_cs & 7) || (Cin & 7) || (Cout & 7)) return MI_ERR_UNSUPPORTED;
   if (colsum && colsum_stride != 0 && (V & 255)) return MI_ERR_UNSUPPORTED;  // tiles must not straddle images for per-image sums
+  mi_conv_note_kernel(MI_CK_WG_1X1);
   W11Args p;
   p.x = (const bf16*)x; p.x_cs = x_cs; p.Cin = Cin; p.dy = (const bf16*)dy; p.dy_cs = dy_cs; p.Cout = Cout;
   p.dw = dw; p.colsum = colsum; p.colsum_stride = colsum_stride; p.nvox = (int64_t)N * V; p.vox_per_image = V;

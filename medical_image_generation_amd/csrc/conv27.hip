@@ -62,6 +62,7 @@ int launch27r(ConvArgs a, int ntiles, int ny, hipStream_t st) {
     attr_set = true;
   }
   static_assert(KK::LDS_TOTAL <= 160 * 1024, "LDS budget of the rolling variant");
+  mi_conv_note_kernel(FLIP ? MI_CK_C27_ROLL_DG : MI_CK_C27_ROLL_FWD);
   hipLaunchKernelGGL(kern, dim3(gx, ny), dim3(512), (size_t)KK::LDS_TOTAL, st, a);
   MI_CHECK_LAUNCH();
   return 0;
@@ -81,6 +82,7 @@ int launch27(ConvArgs a, int ntiles, int ny, hipStream_t st) {
     if (e != hipSuccess) return (int)e;
     attr_set = true;
   }
+  mi_conv_note_kernel(NCB == 2 ? (FLIP ? MI_CK_C27_2_DG : MI_CK_C27_2_FWD) : (FLIP ? MI_CK_C27_1_DG : MI_CK_C27_1_FWD));
   hipLaunchKernelGGL(kern, dim3(gx, ny), dim3(512), (size_t)KK::LDS_TOTAL, st, a);
   MI_CHECK_LAUNCH();
   if (a.dbg & 64) {  // diagnostic only: synchronises

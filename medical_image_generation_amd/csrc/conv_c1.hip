@@ -434,6 +434,7 @@ int mi_launch_c1_expand(const void* s, int s_cs, const float* w, const float* ad
   if (tiles >= (1ll << 31)) return MI_ERR_UNSUPPORTED;
   const int grid = (int)(tiles < 2048 ? tiles : 2048);  // persistent: 8 workgroups of 4 waves per CU
   const int ncb = (C + 31) / 32;
+  mi_conv_note_kernel(MI_CK_C1_EXPAND);
   if (ncb == 1) {
     if (flip) hipLaunchKernelGGL((k_c1_expand_mfma<1, 1>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
     else hipLaunchKernelGGL((k_c1_expand_mfma<1, 0>), dim3(grid), dim3(256), 0, st, a, (int)tiles);
@@ -462,6 +463,7 @@ int mi_launch_c1_reduce(const void* x, int x_cs, const float* w, const float* ad
     if (e != hipSuccess) return (int)e;
     attr_done[nk - 1] = true;
   }
+  mi_conv_note_kernel(MI_CK_C1_REDUCE);
   hipLaunchKernelGGL(k, dim3((unsigned)tiles), dim3(256), lds, st, a);
   MI_CHECK_LAUNCH();
   return 0;
@@ -495,6 +497,7 @@ int mi_launch_c1_wgrad(const void* m, int m_cs, const void* s1, int s_cs, float*
       if (e != hipSuccess) return (int)e;
       attr_done[ncb - 1] = true;
     }
+    mi_conv_note_kernel(MI_CK_WG_C1);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a);
   }
   const int slab = ncb * 1024 + 32;

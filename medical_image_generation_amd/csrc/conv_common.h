@@ -121,6 +121,8 @@ static __device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* b
 }  // namespace mi_conv
 using namespace mi_conv;
 
+// conv.hip: records the kernel family (enum mi_conv_kernel) a launch site is about to launch, for mi_conv_last_kernel (a thread_local store)
+void mi_conv_note_kernel(int id);
 // conv27.hip: k3 s1 p1 3-D forward (flip = 0) / data gradient (flip = 1) on the 4x8x8 tile; a.g / tables as for the table-driven kernel
 int mi_launch_conv27(const ConvArgs& a, int NCB, int flip, int ntiles, int ny, hipStream_t st);
 int mi_conv27_grid_x(int ntiles, int ny);  // gridDim.x of that launch (4 statistics chunks per workgroup)

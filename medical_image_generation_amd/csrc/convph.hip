@@ -42,6 +42,7 @@ int launchph(ConvArgs a, int ntiles, int ny, hipStream_t st) {
     attr_set = true;
   }
   static_assert(KK::LDS_TOTAL <= 160 * 1024, "LDS budget");
+  mi_conv_note_kernel(MODE == 1 ? (NCB == 2 ? MI_CK_PH_SCATTER_64 : MI_CK_PH_SCATTER_32) : (NCB == 2 ? MI_CK_PH_GATHER_64 : MI_CK_PH_GATHER_32));
   hipLaunchKernelGGL(kern, dim3(gx, ny), dim3(512), (size_t)KK::LDS_TOTAL, st, a);
   MI_CHECK_LAUNCH();
   return 0;

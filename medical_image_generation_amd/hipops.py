@@ -273,6 +273,16 @@ class ConvPlan:
         assert weight_f32.dtype == F32 and weight_f32.is_contiguous()
         call("mi_conv_pack_weights", self.handle, ptr(weight_f32))
 
+    @staticmethod
+    def last_kernel() -> int:
+        """`enum mi_conv_kernel` id of the kernel the most recent fwd / dgrad / wgrad of this thread launched (tests)."""
+        return int(_lib.call_raw("mi_conv_last_kernel"))
+
+    @property
+    def wgrad_splits(self) -> int:
+        """Splits of the tile range the tiled weight-gradient kernels of this plan run with (tests)."""
+        return int(_lib.call_raw("mi_conv_plan_wgrad_splits", self.handle))
+
     def fwd(self, x, st: GNStats | None = None, silu=False, addvec=None, res=None, out=None, want_sums=False):
         """out: optional destination, a channel-slice view [N, D, H, W, Cout] of a wider channels-last buffer (the conv writes
         straight into the skip-concat buffer of its consumer instead of being copied there).  want_sums: also return the
