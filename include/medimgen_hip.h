@@ -33,7 +33,6 @@ int mi_abi_version(void);
 int mi_ncdhw_f32_to_ndhwc_bf16(const float* src, void* dst, int N, int C, int64_t V, hipStream_t stream);
 int mi_ndhwc_bf16_to_ncdhw_f32(const void* src, float* dst, int N, int C, int64_t V, hipStream_t stream);
 int mi_cast_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t stream);
-int mi_cast_bf16_to_f32(const void* src, float* dst, int64_t n, int accumulate, hipStream_t stream);
 
 /* ---- aten::add (residuals UNet:695,701,458; AEKL:204,323), aten::cat (UNet:1263,1377,1504) ------------------------------ */
 int mi_add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t stream);
@@ -110,23 +109,23 @@ int mi_conv_pack_batch_create(mi_pack_batch** out, mi_conv_plan* const* plans, c
 int mi_conv_pack_batch_run(mi_pack_batch* batch, hipStream_t stream);
 int mi_conv_pack_batch_destroy(mi_pack_batch* batch);
 
-/* y = conv(act(x)) + addvec + res;  act = GroupNorm affine (+SiLU) applied on the fly when scale_shift != NULL;
+/* y = conv(x) + addvec + res;  x is the conv's input as it stands (a preceding GroupNorm (+SiLU) is mi_gn_apply's pass);
  * addvec: fp32 [Cout] (addvec_stride 0: bias) or N rows of pitch addvec_stride (bias + time-embedding projection, UNet:692-695) */
-int mi_conv_fwd(mi_conv_plan* plan, const void* x, int x_cstride, const float* scale_shift, int silu, const float* addvec,
-                int addvec_stride, const void* res, int res_cstride, void* y, int y_cstride, float* out_stats, hipStream_t stream);
+int mi_conv_fwd(mi_conv_plan* plan, const void* x, int x_cstride, const float* addvec, int addvec_stride, const void* res, int res_cstride,
+                void* y, int y_cstride, float* out_stats, hipStream_t stream);
 /* out_stats (optional): the k3 s1 p1 3-D kernel (32-channel rows) and the 1 -> C kernel of a network's input conv (C <= 32, no residual)
  * also emit per-channel (sum, sum of squares) of their bf16 output, so the GroupNorm that consumes y (UNet:628, 648) needs no statistics
  * pass over it: fp32 [N][Cout][chunks][2] with chunks = mi_conv_fwd_stats_chunks (0: this plan's forward cannot -- strided / 1x1 / 2-D
  * convs and the 64-channels-per-workgroup variant -- pass NULL), every entry written.  Feed it to mi_gn_stats_from_partial. */
 int mi_conv_fwd_stats_chunks(const mi_conv_plan* plan);
-/* dx = conv_transpose(dy)  (gradient w.r.t. the ACTIVATED input) */
+/* dx = conv_transpose(dy)  (gradient w.r.t. the conv's input x) */
 int mi_conv_dgrad(mi_conv_plan* plan, const void* dy, int dy_cstride, void* dx, int dx_cstride, hipStream_t stream);
-/* dweight += x_act^T * dy   (fp32, torch layout; x_act recomputed from x with the same fused prologue).
+/* dweight += x^T * dy   (fp32, torch layout; x: the tensor mi_conv_fwd was given).
  * dy_colsum (optional, fp32, ACCUMULATED): dy_colsum[n*stride + co] += sum over voxels of dy -- the bias / time-embedding
  * gradient, produced from the dY fragments the kernel already holds (one all-ones MFMA per k-step); stride 0 sums the whole
  * batch into one row (= the bias gradient) */
-int mi_conv_wgrad(mi_conv_plan* plan, const void* x, int x_cstride, const float* scale_shift, int silu, const void* dy, int dy_cstride,
-                  float* dweight, float* dy_colsum, int dy_colsum_stride, hipStream_t stream);
+int mi_conv_wgrad(mi_conv_plan* plan, const void* x, int x_cstride, const void* dy, int dy_cstride, float* dweight, float* dy_colsum,
+                  int dy_colsum_stride, hipStream_t stream);
 /* Which kernel ran (tests): the id of the kernel family that the most recent mi_conv_fwd / mi_conv_dgrad / mi_conv_wgrad of the calling
  * thread launched -- a host-side thread_local stored at each launch site, one value per instantiation family the dispatch can reach.
  * An Upsample + conv plan on its fallback reports its inner plan's kernel.  Not a stream operation; nothing reads it on the hot path. */
@@ -421,7 +420,6 @@ int mi_reparam_kl_bwd(const void* mu, const void* sigma, const float* eps, const
 /* ---- clip_grad_norm_ (T-LDM:177, T-DDPM:196, T-AE:393,431) + torch.optim.Adam / AdamW (T-LDM:121, T-AE:470, T-DDPM:383)
  *      over the flat fp32 parameter arena; step counter and squared norm stay on the device ------------------------------- */
 int mi_sumsq_f32(const float* x, int64_t n, float* out, int accumulate, hipStream_t stream);
-int mi_clip_grad_by_norm(float* grad, int64_t n, const float* grad_sumsq, float max_norm, hipStream_t stream);
 int mi_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr, float beta1, float beta2,
                  float eps, float weight_decay, int decoupled_weight_decay, const float* grad_sumsq, float max_norm, float grad_scale,
                  float* step_counter, hipStream_t stream);

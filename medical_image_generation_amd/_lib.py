@@ -22,7 +22,6 @@ _SIGS = {
     "mi_ncdhw_f32_to_ndhwc_bf16": [_p, _p, _i, _i, _l, _p],
     "mi_ndhwc_bf16_to_ncdhw_f32": [_p, _p, _i, _i, _l, _p],
     "mi_cast_f32_to_bf16": [_p, _p, _l, _p],
-    "mi_cast_bf16_to_f32": [_p, _p, _l, _i, _p],
     "mi_add_bf16": [_p, _p, _p, _l, _p],
     "mi_copy_channels": [_p, _i, _i, _p, _i, _i, _i, _l, _p],
     "mi_upsample_nearest_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
@@ -43,12 +42,12 @@ _SIGS = {
     "mi_conv_pack_batch_create": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _i],
     "mi_conv_pack_batch_run": [_p, _p],
     "mi_conv_pack_batch_destroy": [_p],
-    "mi_conv_fwd": [_p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p],
+    "mi_conv_fwd": [_p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p],
     "mi_conv_fwd_stats_chunks": [_p],
     "mi_conv_last_kernel": [],
     "mi_conv_plan_wgrad_splits": [_p],
     "mi_conv_dgrad": [_p, _p, _i, _p, _i, _p],
-    "mi_conv_wgrad": [_p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _p],
+    "mi_conv_wgrad": [_p, _p, _i, _p, _i, _p, _p, _i, _p],
     "mi_linear_wgrad_bf16": [_p, _i, _i, _p, _i, _i, _l, _p, _p, _p],
     "mi_colsum_bf16": [_p, _p, _i, _i, _l, _i, _i, _p],
     "mi_add_f32_2d": [_p, _i, _p, _i, _i, _i, _p],
@@ -119,7 +118,6 @@ _SIGS = {
     "mi_reparam_kl_fwd": [_p, _p, _p, _p, _p, _i, _i, _l, _f, _p],
     "mi_reparam_kl_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _l, _f, _p],
     "mi_sumsq_f32": [_p, _l, _p, _i, _p],
-    "mi_clip_grad_by_norm": [_p, _l, _p, _f, _p],
     "mi_adam_step": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _f, _f, _p, _p],
     "mi_adam_step_dev": [_p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
     "mi_adam_ema_step_dev": [_p, _p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
@@ -140,7 +138,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 16
+ABI_VERSION = 17
 
 
 def exported_symbols() -> list[str]:

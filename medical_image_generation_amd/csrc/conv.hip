@@ -19,8 +19,9 @@
 //   * B operand: the workgroup stages a halo tile (TD+2)x(TH+2)x(TW+2) voxels x 32 channels of x in LDS ONCE per channel
 //     chunk and every tap reads it at a wave-uniform byte offset -> each activation byte is fetched ~2x from L2/HBM instead
 //     of 27x.  Voxel pitch 80 B and row pitch == 128 (mod 256) make the 4x8-voxel fragment reads (ds_read_b128)
-//     bank-conflict-free.  Staging goes through registers (issue-early / write-late) because it also applies the fused
-//     GroupNorm-affine + SiLU prologue (x*scale[n,c]+shift[n,c] -> silu) in fp32 -- the activated tensor never exists in HBM.
+//     bank-conflict-free.  Staging goes through registers (issue-early / write-late), which is what lets this kernel take
+//     what the LDS-DMA kernels (conv27.hip, convph.hip, k_conv_wgrad2 / 3) do not: channel counts that are no multiple of 8 (masked
+//     element-wise loads) and every geometry of the tap tables (strided, 2-D, odd tiles).  It is the general route, not the fast one.
 //   * A operand: fragments are pre-packed in consumption order (one coalesced 1 KiB global_load_dwordx4 per fragment, served
 //     from L2 -- weights are shared by every workgroup) and double-buffered in registers across taps.
 //   * Epilogue: + (bias [+ time-embedding]) per (n, co), + residual, cast, store.
@@ -47,7 +48,6 @@ template <int NP>
 struct Stage {
   int pk[NP];      // (hd << 20) | (hh << 10) | hw, or -1 for pieces beyond the image
   u32x4 pre[NP];   // staged data (next image), in flight while the current image is consumed
-  unsigned valid;  // bit i: piece i lies inside the tensor (prologue applies only there: zero padding stays zero)
 };
 
 template <int NP, int NT = 256>
@@ -61,7 +61,6 @@ __device__ __forceinline__ void stage_init(Stage<NP>& s, const Geom& g) {
     int hhz = rem / g.HW, hwz = rem - hhz * g.HW;
     s.pk[i] = v < HVOX ? ((hdz << 20) | (hhz << 10) | hwz) : -1;
   }
-  s.valid = 0;
 }
 
 // Wave-uniform buffer descriptor (raw, no stride): 32-bit per-lane byte offsets, hardware range check (an offset beyond
@@ -77,13 +76,11 @@ __device__ __forceinline__ void stage_load(Stage<NP>& s, const ConvArgs& a, int 
   const int c = src_c0 + part * 8;
   const bool vec = ((a.x_cs & 7) == 0) && (c + 8 <= a.Cin);
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
-  unsigned valid = 0;
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int pk = s.pk[i];
     const int gd = d0 - g.hd + (pk >> 20), gh = h0 - g.hh + ((pk >> 10) & 1023), gw = w0 - g.hw + (pk & 1023);
     const bool ok = pk >= 0 && gd >= 0 && gd < a.Di && gh >= 0 && gh < a.Hi && gw >= 0 && gw < a.Wi;
-    valid |= ok ? (1u << i) : 0u;
     const unsigned off = ok ? (unsigned)((((n * a.Di + gd) * a.Hi + gh) * a.Wi + gw) * a.x_cs + c) * 2u : 0xffffffffu;
     if (vec) {
       s.pre[i] = buf_load16(rx, off, 0);  // out-of-range offset -> zeros
@@ -99,38 +96,16 @@ __device__ __forceinline__ void stage_load(Stage<NP>& s, const ConvArgs& a, int 
       s.pre[i] = v;
     }
   }
-  s.valid = valid;
 }
 
 template <int NP>
-__device__ __forceinline__ void stage_store(Stage<NP>& s, const ConvArgs& a, int n, int src_c0, char* lds) {
-  const Geom& g = a.g;
+__device__ __forceinline__ void stage_store(const Stage<NP>& s, const Geom& g, char* lds) {
   const int part = threadIdx.x & 3;
-  float sc[8], sh[8];
-  if (a.ss) {
-    const int c = (src_c0 % a.ss_C) + part * 8;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      bool in = c + j < a.ss_C;
-      sc[j] = in ? a.ss[((int64_t)n * a.ss_C + c + j) * 2] : 0.f;
-      sh[j] = in ? a.ss[((int64_t)n * a.ss_C + c + j) * 2 + 1] : 0.f;
-    }
-  }
 #pragma unroll
   for (int i = 0; i < NP; ++i) {
     const int pk = s.pk[i];
     if (pk < 0) continue;
-    u32x4 v = s.pre[i];
-    if (a.ss && ((s.valid >> i) & 1u)) {
-      F8 f = unpack8(v);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float u = f.v[j] * sc[j] + sh[j];
-        f.v[j] = a.pro_silu ? silu_f(u) : u;
-      }
-      v = pack8(f);
-    }
-    *(u32x4*)(lds + (pk >> 20) * g.slice + ((pk >> 10) & 1023) * g.row + (pk & 1023) * g.vox + part * 16) = v;
+    *(u32x4*)(lds + (pk >> 20) * g.slice + ((pk >> 10) & 1023) * g.row + (pk & 1023) * g.vox + part * 16) = s.pre[i];
   }
 }
 
@@ -244,10 +219,10 @@ __device__ __forceinline__ void f27_taps3(f32x16 (&acc)[VB][NCB], u32x4 (&wa)[RI
   }
 }
 
-template <int NCB, int VB, int NP, int RING, int WPS, int MODE>  // MODE 0: table-driven taps, 1: k3-s1 forward, 2: k3-s1 dgrad
-__global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
+template <int NCB, int VB, int NP, int RING, int MODE>  // MODE 0: table-driven taps, 1: k3-s1 forward, 2: k3-s1 dgrad
+__global__ void __launch_bounds__(256, 2) k_conv_igemm(ConvArgs a) {  // two workgroups per CU overlap staging with MFMA
   constexpr bool FULL27 = MODE != 0;
-  constexpr int FLIP = MODE == 2;  // WPS = 2: two workgroups per CU overlap staging with MFMA
+  constexpr int FLIP = MODE == 2;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int r = lane & 31, h = lane >> 5;
@@ -273,7 +248,6 @@ __global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
   Stage<NP> st;
   stage_init<NP>(st, g);
   stage_load<NP>(st, a, n, d0, h0, w0, hdr[2]);
-  int n_pre = n;  // batch index of the data held in st.pre
   bool first_img = true;
 
   while (true) {
@@ -288,7 +262,7 @@ __global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
     int nn = 0, nd0 = 0, nh0 = 0, nw0 = 0;
 
     for (int ch = 0; ch < a.nchunks; ++ch) {
-      const int tap_begin = hdr[ch * 4 + 0], ntaps = hdr[ch * 4 + 1], src_c0 = hdr[ch * 4 + 2], wfrag = hdr[ch * 4 + 3];
+      const int tap_begin = hdr[ch * 4 + 0], ntaps = hdr[ch * 4 + 1], wfrag = hdr[ch * 4 + 3];
       // weight ring: the first RING taps' fragments are requested BEFORE the staging phase, which hides their L2 latency
       const __amdgpu_buffer_rsrc_t rw = make_rsrc(a.wpk, a.wpk_bytes);
       const unsigned wsoff = (unsigned)wfrag * 1024u;  // scalar byte offset of this chunk's first fragment
@@ -303,7 +277,7 @@ __global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
             for (int cb = 0; cb < NCB; ++cb) wa[q][ks][cb] = buf_load16(rw, wlane, wsoff + ((q * 2 + ks) * NCB + cb) * 1024u);
         }
       __syncthreads();  // every wave is done reading the previous tile image
-      if (a.dbg != 1 || first_img) stage_store<NP>(st, a, n_pre, src_c0, lds);
+      if (a.dbg != 1 || first_img) stage_store<NP>(st, g, lds);
       __syncthreads();
       first_img = false;
       // next image (next chunk of this tile, or chunk 0 of this workgroup's next tile): in flight under the MFMAs below
@@ -314,7 +288,6 @@ __global__ void __launch_bounds__(256, WPS) k_conv_igemm(ConvArgs a) {
       } else if (next_tile < tile_last) {
         tile_origin(g, next_tile, nn, nd0, nh0, nw0);
         stage_load<NP>(st, a, nn, nd0, nh0, nw0, hdr[2]);
-        n_pre = nn;
       }
       if (a.dbg == 2) continue;
       if constexpr (FULL27) {
@@ -722,7 +695,7 @@ __global__ void __launch_bounds__(512, 2) k_conv_wgrad(WgradArgs w) {
   while (true) {
     __syncthreads();  // previous tile fully consumed
     if ((w.dbg != 1 && w.dbg < 3) || first) {
-      stage_store<NP>(st, a, n, src_c0, lds);
+      stage_store<NP>(st, g, lds);
       stagey_store<NPY, NT>(sy, g, ldy);
     }
     __syncthreads();
@@ -2225,7 +2198,7 @@ int pick_nsplit(int ntiles, int npairs, int fixed_tiles) {
   return nsplit;
 }
 
-template <int NCB, int VB, int RING, int WPS, int MODE>
+template <int NCB, int VB, int RING, int MODE>
 int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   if (MODE != 0 && (a.g.row != F27_ROW || a.g.slice != F27_SLICE || a.g.TD != 4 || a.g.TH != 8 || a.g.TW != 8)) return MI_ERR_BAD_ARG;
   const int hv = a.g.HD * a.g.HH * a.g.HW;
@@ -2234,7 +2207,7 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   static const int dbg = mi_diag_knob("MI_IGEMM_DBG");
   a.dbg = dbg;
   // persistent grid: ~2 workgroups per CU in total, a multiple of 8 per cout group (one slot set per XCD residue class)
-  int gx = (256 * WPS / ny + 7) / 8 * 8;
+  int gx = (256 * 2 / ny + 7) / 8 * 8;
   if (gx < 8) gx = 8;
   int need = (ntiles + 7) / 8 * 8;
   if (gx > need) gx = need;
@@ -2242,7 +2215,7 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
   size_t lds = (size_t)a.g.lds_bytes;
 #define MI_LAUNCH_NP(NPV)                                                                                  \
   do {                                                                                                     \
-    auto kern = k_conv_igemm<NCB, VB, NPV, RING, WPS, MODE>;                                               \
+    auto kern = k_conv_igemm<NCB, VB, NPV, RING, MODE>;                                                    \
     static bool raised = false; /* one flag per instantiation */                                           \
     if (int e = raise_lds_limit((const void*)kern, raised)) return e;                                      \
     mi_conv_note_kernel(MODE == 0 ? (NCB == 2 ? MI_CK_IGEMM_M0_64 : MI_CK_IGEMM_M0_32)                     \
@@ -2266,12 +2239,11 @@ int launch_igemm(ConvArgs a, int ntiles, int ny, hipStream_t st) {
 }
 
 int launch_igemm_any(const ConvArgs& a, int NCB, int mode, int ntiles, int ny, hipStream_t st) {
-  // <NCB, VB, RING, WPS, MODE>: two workgroups per CU everywhere; weight-fragment ring of 2 taps in the 64-cout-per-workgroup variant, of 3
-  // taps in the 32-cout variant
-  if (mode == 1) return NCB == 2 ? launch_igemm<2, 2, 2, 2, 1>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 2, 1>(a, ntiles, ny, st);
-  if (mode == 2) return NCB == 2 ? launch_igemm<2, 2, 2, 2, 2>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 2, 2>(a, ntiles, ny, st);
-  if (NCB == 2) return launch_igemm<2, 2, 2, 2, 0>(a, ntiles, ny, st);
-  return launch_igemm<1, 2, 4, 2, 0>(a, ntiles, ny, st);
+  // <NCB, VB, RING, MODE>: weight-fragment ring of 2 taps in the 64-cout-per-workgroup variant, of 3 taps in the 32-cout variant
+  if (mode == 1) return NCB == 2 ? launch_igemm<2, 2, 2, 1>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 1>(a, ntiles, ny, st);
+  if (mode == 2) return NCB == 2 ? launch_igemm<2, 2, 2, 2>(a, ntiles, ny, st) : launch_igemm<1, 2, 3, 2>(a, ntiles, ny, st);
+  if (NCB == 2) return launch_igemm<2, 2, 2, 0>(a, ntiles, ny, st);
+  return launch_igemm<1, 2, 4, 0>(a, ntiles, ny, st);
 }
 
 // ---- phase convolutions (convph.hip) -----------------------------------------------------------------------------------------------
@@ -2863,15 +2835,15 @@ int mi_conv_fwd_stats_chunks(const mi_conv_plan* P) {
 
 // ---- routes of mi_conv_fwd that are more than one launch call, in the order the entry point tries them
 // Upsample + conv, fallback: materialise the nearest-upsampled tensor, plain k3 s1 conv on the fine grid
-static int fwd_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
-                               const void* res, int res_cs, void* y, int y_cs, hipStream_t st) {
+static int fwd_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const float* addvec, int addvec_stride, const void* res, int res_cs,
+                               void* y, int y_cs, hipStream_t st) {
   if (x_cs != P->Cin) return MI_ERR_UNSUPPORTED;
   if (int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st)) return e;
-  return mi_conv_fwd(P->up_inner, P->d_xup, P->Cin, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, nullptr, st);
+  return mi_conv_fwd(P->up_inner, P->d_xup, P->Cin, addvec, addvec_stride, res, res_cs, y, y_cs, nullptr, st);
 }
 // arguments of the three tiled kernels (1x1 streaming, conv27, table-driven); a strided conv reads the space-to-depth image of x, made here
-static int fwd_args(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
-                    const void* res, int res_cs, void* y, int y_cs, ConvArgs& a, int& ntiles, hipStream_t st) {
+static int fwd_args(mi_conv_plan* P, const void* x, int x_cs, const float* addvec, int addvec_stride, const void* res, int res_cs, void* y,
+                    int y_cs, ConvArgs& a, int& ntiles, hipStream_t st) {
   memset(&a, 0, sizeof(a));
   a.x = (const bf16*)x; a.x_cs = x_cs; a.N = P->N; a.Di = P->Di; a.Hi = P->Hi; a.Wi = P->Wi; a.Cin = P->Cin;
   if (P->strided) {
@@ -2880,7 +2852,6 @@ static int fwd_args(mi_conv_plan* P, const void* x, int x_cs, const float* scale
   }
   a.y = (bf16*)y; a.y_cs = y_cs; a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
   a.ogpq = P->fwd.ny; a.outc_q = P->Cout;
-  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
   a.addvec = addvec; a.addvec_stride = addvec_stride;
   a.res = (const bf16*)res; a.res_cs = res_cs;
   a.perm16 = P->v27_fwd || P->v11_fwd;
@@ -2895,16 +2866,16 @@ static int fwd_conv27(mi_conv_plan* P, ConvArgs& a, int ntiles, float* out_stats
   return mi_launch_conv27(a, P->ncb_fwd, 0, ntiles, P->fwd.ny, st);
 }
 
-int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const float* addvec, int addvec_stride,
-                const void* res, int res_cs, void* y, int y_cs, float* out_stats, hipStream_t st) {
+int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* addvec, int addvec_stride, const void* res, int res_cs, void* y,
+                int y_cs, float* out_stats, hipStream_t st) {
   if (!P || !x || !y || x_cs < P->Cin || y_cs < P->Cout) return MI_ERR_BAD_ARG;
-  if (out_stats && (!mi_conv_fwd_stats_chunks(P) || scale_shift || ((x_cs & 7) && !P->c1_in))) return MI_ERR_UNSUPPORTED;  // conv27 / 1 -> C paths only
-  if (P->ph_fwd.mode && !scale_shift && !res) {  // Upsample + conv (scatter) / k3 s2 conv (gather) on the phase kernels
+  if (out_stats && (!mi_conv_fwd_stats_chunks(P) || ((x_cs & 7) && !P->c1_in))) return MI_ERR_UNSUPPORTED;  // conv27 / 1 -> C paths only
+  if (P->ph_fwd.mode && !res) {  // Upsample + conv (scatter) / k3 s2 conv (gather) on the phase kernels
     const int e = phase_side_run(P->ph_fwd, x, x_cs, P->Di, P->Hi, P->Wi, y, y_cs, P->Do, P->Ho, P->Wo, P->N, addvec, addvec_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  if (P->up) return fwd_upconv_fallback(P, x, x_cs, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, st);
-  if ((P->c1_in || P->c1_out) && P->c1_packed && !scale_shift && !res) {  // one channel on one side (conv_c1.hip)
+  if (P->up) return fwd_upconv_fallback(P, x, x_cs, addvec, addvec_stride, res, res_cs, y, y_cs, st);
+  if ((P->c1_in || P->c1_out) && P->c1_packed && !res) {  // one channel on one side (conv_c1.hip)
     if (out_stats && !P->c1_in) return MI_ERR_UNSUPPORTED;
     const int e = P->c1_in ? mi_launch_c1_expand(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st, out_stats)
                            : mi_launch_c1_reduce(x, x_cs, P->d_c1w, addvec, addvec_stride, y, y_cs, P->N, P->Di, P->Hi, P->Wi, P->Cin, st);
@@ -2913,18 +2884,18 @@ int mi_conv_fwd(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shi
   if (out_stats && P->c1_in) return MI_ERR_UNSUPPORTED;  // (the table-driven fallback of a single-channel conv emits no sums: never silently)
   ConvArgs a;
   int ntiles;
-  if (int e = fwd_args(P, x, x_cs, scale_shift, silu, addvec, addvec_stride, res, res_cs, y, y_cs, a, ntiles, st)) return e;
-  if (P->g11 && !P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0 && (y_cs & 7) == 0 && addvec_stride == 0 && !out_stats &&
+  if (int e = fwd_args(P, x, x_cs, addvec, addvec_stride, res, res_cs, y, y_cs, a, ntiles, st)) return e;
+  if (P->g11 && !P->v11_fwd && !res && (x_cs & 7) == 0 && (y_cs & 7) == 0 && addvec_stride == 0 && !out_stats &&
       ((uintptr_t)x & 15) == 0 && (int64_t)P->N * P->Do * P->Ho * P->Wo < (1ll << 31)) {  // 1x1 on the NT GEMM: y[vox][co] = x[vox][:] . W[co][:] + bias
     mi_conv_note_kernel(MI_CK_1X1_GEMM);
     return mi_gemm_nt_bf16(x, x_cs, 0, 0, P->d_w11, P->Cin, 0, 0, y, y_cs, 0, 0, addvec, nullptr, 0, 0, 0, P->N * P->Do * P->Ho * P->Wo, P->Cout, P->Cin, 1, 1,
                            1.0f, 0, 0, st);
   }
-  if (P->v11_fwd && !scale_shift && !res && (x_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
+  if (P->v11_fwd && !res && (x_cs & 7) == 0) {  // 1x1 streaming kernel (conv1x1.hip)
     a.y_bytes = span32(P->N, P->Do, P->Ho, P->Wo, y_cs);  // (0: unbounded)
     return mi_launch_conv1x1(a, P->ncb_fwd, P->fwd.ny, st);
   }
-  if (P->v27_fwd && !scale_shift) {  // (the fused GroupNorm prologue lives in the register-staged kernel)
+  if (P->v27_fwd) {  // conv27.hip
     if (x_cs & 7) return MI_ERR_UNSUPPORTED;
     const int e = fwd_conv27(P, a, ntiles, out_stats, st);
     if (e != MI_ERR_UNSUPPORTED || out_stats) return e;
@@ -2991,25 +2962,25 @@ int mi_conv_dgrad(mi_conv_plan* P, const void* dy, int dy_cs, void* dx, int dx_c
 }
 
 // Upsample + conv, fallback: on the fine grid against the nearest-upsampled x
-static int wgrad_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, const void* dy, int dy_cs, float* dw,
-                                 float* dy_colsum, int dy_colsum_stride, hipStream_t st) {
-  if (x_cs != P->Cin || scale_shift) return MI_ERR_UNSUPPORTED;
+static int wgrad_upconv_fallback(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int dy_cs, float* dw, float* dy_colsum,
+                                 int dy_colsum_stride, hipStream_t st) {
+  if (x_cs != P->Cin) return MI_ERR_UNSUPPORTED;
   if (int e = mi_upsample_nearest_fwd(x, P->d_xup, P->N, P->Di, P->Hi, P->Wi, P->Cin, 2, 2, 2, st)) return e;
-  return mi_conv_wgrad(P->up_inner, P->d_xup, P->Cin, nullptr, 0, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
+  return mi_conv_wgrad(P->up_inner, P->d_xup, P->Cin, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
 }
 // Arguments of the tiled weight-gradient kernels, and which of the two families runs: `dma` = the LDS-DMA kernels (launch_wgrad_dma: whole
-// 8-channel pieces only, no fused prologue), else the register-staged ones (launch_wgrad_regs).  A k3 s2 conv on all axes has the LDS-DMA
+// 8-channel pieces only), else the register-staged ones (launch_wgrad_regs).  A k3 s2 conv on all axes has the LDS-DMA
 // kernel gather each pair's class image from x in place (`direct`: d_hdr2, sx = 2 -- no space-to-depth copy); the register-staged kernel
 // understands neither, so direct => dma.  Every other strided conv reads the space-to-depth image of x, made here.
-static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const void* dy, int dy_cs, float* dy_colsum,
-                      int dy_colsum_stride, WgradArgs& w, bool& dma, bool& direct, hipStream_t st) {
+static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int dy_cs, float* dy_colsum, int dy_colsum_stride,
+                      WgradArgs& w, bool& dma, bool& direct, hipStream_t st) {
   memset(&w, 0, sizeof(w));
   ConvArgs& a = w.c;
   const Geom& g = P->g_wg;
   static const int use_w2 = mi_env_int("MI_WGRAD2", 1);
   const int nvox = g.TD * g.TH * g.TW, px = (g.lds_bytes + 1023) / 1024, py = (nvox * 64 + 1023) / 1024;
   const unsigned dyb = span32(P->N, P->Do, P->Ho, P->Wo, dy_cs);
-  const bool dma_ok = use_w2 && !scale_shift && g.vox == 64 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && px <= 40 && py <= 16 && dyb;
+  const bool dma_ok = use_w2 && g.vox == 64 && (dy_cs & 7) == 0 && (P->Cout & 7) == 0 && px <= 40 && py <= 16 && dyb;
   direct = P->s2_wg_direct && dma_ok && (x_cs & 7) == 0 && span32(P->N, P->Di, P->Hi, P->Wi, x_cs);
   const bool s2d = P->strided && !direct;
   a.x = s2d ? P->d_xs : (const bf16*)x; a.x_cs = s2d ? P->Q * P->Cin : x_cs; a.N = P->N;
@@ -3022,7 +2993,6 @@ static int wgrad_args(mi_conv_plan* P, const void* x, int x_cs, const float* sca
   a.Cout = P->Cout; a.Do = P->Do; a.Ho = P->Ho; a.Wo = P->Wo;
   a.hdr = direct ? P->d_hdr2 : P->wg.d_hdr; a.taps = P->wg.d_taps; a.nchunks = P->wg.nchunks;
   w.sx = direct ? 2 : 1; w.sy = 1; w.cs_chunks = 1;
-  a.ss = scale_shift; a.ss_C = P->Cin; a.pro_silu = silu;
   if (!(a.x_bytes = span32(a.N, a.Di, a.Hi, a.Wi, a.x_cs))) return MI_ERR_UNSUPPORTED;
   a.g = g;
   w.dy = (const bf16*)dy; w.dy_cs = dy_cs; w.dy_bytes = dma ? dyb : 0u;
@@ -3099,22 +3069,22 @@ static int launch_wgrad_regs(const mi_conv_plan* P, const WgradArgs& w, hipStrea
   return 0;
 }
 
-// dw (fp32, torch layout [Cout][Cin][kd][kh][kw]) += wgrad;  x side takes the same fused prologue as the forward
-int mi_conv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const float* scale_shift, int silu, const void* dy, int dy_cs, float* dw,
-                  float* dy_colsum, int dy_colsum_stride, hipStream_t st) {
+// dw (fp32, torch layout [Cout][Cin][kd][kh][kw]) += wgrad
+int mi_conv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const void* dy, int dy_cs, float* dw, float* dy_colsum, int dy_colsum_stride,
+                  hipStream_t st) {
   if (!P || !x || !dy || !dw || x_cs < P->Cin || dy_cs < P->Cout) return MI_ERR_BAD_ARG;
-  if (P->up && P->up_wg && !scale_shift && (x_cs & 7) == 0 && (dy_cs & 7) == 0) {  // Upsample + conv by phase pairs on the coarse grid
+  if (P->up && P->up_wg && (x_cs & 7) == 0 && (dy_cs & 7) == 0) {  // Upsample + conv by phase pairs on the coarse grid
     const int e = upconv_wgrad(P, x, x_cs, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
-  if (P->up) return wgrad_upconv_fallback(P, x, x_cs, scale_shift, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
+  if (P->up) return wgrad_upconv_fallback(P, x, x_cs, dy, dy_cs, dw, dy_colsum, dy_colsum_stride, st);
   static const int use_w11 = mi_env_int("MI_WGRAD1X1", 1);
-  if (use_w11 && P->KT == 1 && !P->strided && !scale_shift && !(dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout)) {
+  if (use_w11 && P->KT == 1 && !P->strided && !(dy_colsum && dy_colsum_stride != 0 && dy_colsum_stride < P->Cout)) {
     const int e = mi_launch_wgrad1x1(x, x_cs, P->Cin, dy, dy_cs, P->Cout, P->N, (int64_t)P->Di * P->Hi * P->Wi, dw, dy_colsum, dy_colsum_stride, st);
     if (e != MI_ERR_UNSUPPORTED) return e;
   }
   static const int use_c1w = mi_env_int("MI_C1_WGRAD", 1);
-  if (use_c1w && (P->c1_in || P->c1_out) && P->d_c1part && !scale_shift && !(dy_colsum && dy_colsum_stride != 0)) {
+  if (use_c1w && (P->c1_in || P->c1_out) && P->d_c1part && !(dy_colsum && dy_colsum_stride != 0)) {
     // one channel on one side: a streaming kernel with the 27 taps as the GEMM's N axis (conv_c1.hip) instead of padding that side to 32
     const int e = P->c1_in ? mi_launch_c1_wgrad(dy, dy_cs, x, x_cs, dw, dy_colsum, nullptr, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cout, 0, st)
                            : mi_launch_c1_wgrad(x, x_cs, dy, dy_cs, dw, nullptr, dy_colsum, P->d_c1part, P->N, P->Di, P->Hi, P->Wi, P->Cin, 1, st);
@@ -3123,7 +3093,7 @@ int mi_conv_wgrad(mi_conv_plan* P, const void* x, int x_cs, const float* scale_s
   // tiled: split partial sums into the plan's slabs, then one reduce into dw (and the column sums)
   WgradArgs w;
   bool dma, direct;
-  if (int e = wgrad_args(P, x, x_cs, scale_shift, silu, dy, dy_cs, dy_colsum, dy_colsum_stride, w, dma, direct, st)) return e;
+  if (int e = wgrad_args(P, x, x_cs, dy, dy_cs, dy_colsum, dy_colsum_stride, w, dma, direct, st)) return e;
   if (int e = dma ? launch_wgrad_dma(P, w, direct, st) : launch_wgrad_regs(P, w, st)) return e;
   launch_wgrad_reduce(P->d_part, P->wg_split_stride, P->wg_nsplit, P->d_uitems, P->wg_nitems, dw, P->Cout, P->Cin, P->KT, P->d_pair_off, w.npairs,
                       CsReduce{w.cs_part ? P->d_cspart : nullptr, P->wg_nsplit, P->N, P->Cout, dy_colsum, dy_colsum_stride, 0}, st);

@@ -125,7 +125,7 @@ int launch11(const ConvArgs& a, int ncb_total, int NCB, int nfrags, int64_t nvox
 // a: ConvArgs as filled for the table-driven kernel (x / Cin = tensor the loader reads, y / Cout = tensor produced, wpk packed with
 // the perm16 row order); NCB = cout blocks per packed group, ny = groups.
 int mi_launch_conv1x1(const ConvArgs& a, int NCB, int ny, hipStream_t st) {
-  if ((a.x_cs & 7) || (a.Cin & 7) || a.res || a.ss) return MI_ERR_BAD_ARG;
+  if ((a.x_cs & 7) || (a.Cin & 7) || a.res) return MI_ERR_BAD_ARG;
   const int nch = a.nchunks;
   const int nfrags = ny * nch * 2 * NCB;
   if (nfrags * 1024 > 96 * 1024) return MI_ERR_UNSUPPORTED;

@@ -28,7 +28,6 @@ struct ConvArgs {
   const int* hdr;               // [ny][nchunks][4] = tap_begin, ntaps, src_c0, wfrag_begin
   const int* taps;              // LDS byte offsets
   int nchunks;
-  const float* ss; int ss_C; int pro_silu;  // prologue affine [N][ss_C][2] (channel = src channel % ss_C) or null
   const float* addvec; int addvec_stride;   // fp32 [Cout] (stride 0) or [N] rows of pitch `stride`; null = none
   const bf16* res; int res_cs;
   unsigned y_bytes;             // size of the output tensor for its buffer descriptor (0: >= 4 GiB)

@@ -48,10 +48,6 @@ __global__ void k_add_bf16_tail(const bf16* a, const bf16* b, bf16* o, int64_t s
 __global__ void k_cast_f32_bf16(const float* __restrict__ s, bf16* __restrict__ d, int64_t n) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) d[i] = f2bf(s[i]);
 }
-__global__ void k_cast_bf16_f32(const bf16* __restrict__ s, float* __restrict__ d, int64_t n, int accumulate) {
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    d[i] = accumulate ? d[i] + bf2f(s[i]) : bf2f(s[i]);
-}
 
 // ---------------------------------------------------------------- channel-range copy (concat / split)
 // dst[v][c0d + c] = src[v][c0s + c], c in [0, nC); nC, Cs, Cd, c0s, c0d all multiples of 8
@@ -531,12 +527,6 @@ int mi_add_bf16(const void* a, const void* b, void* out, int64_t n, hipStream_t 
 int mi_cast_f32_to_bf16(const float* src, void* dst, int64_t n, hipStream_t st) {
   if (n <= 0) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_cast_f32_bf16, dim3(grid_for(n)), dim3(kThreads), 0, st, src, (bf16*)dst, n);
-  MI_CHECK_LAUNCH();
-  return 0;
-}
-int mi_cast_bf16_to_f32(const void* src, float* dst, int64_t n, int accumulate, hipStream_t st) {
-  if (n <= 0) return MI_ERR_BAD_ARG;
-  hipLaunchKernelGGL(k_cast_bf16_f32, dim3(grid_for(n)), dim3(kThreads), 0, st, (const bf16*)src, dst, n, accumulate);
   MI_CHECK_LAUNCH();
   return 0;
 }

@@ -4,7 +4,7 @@
 // streaming kernel (16-byte loads, 8 channels per lane, LDS reduction over the voxel lanes of the block), then one
 // small block per (n, group) finishes in fp64 and emits the per-(n, channel) affine pair
 //     scale = gamma * rstd,   shift = beta - mean * scale
-// that conv prologues / the apply kernel consume, so "normalise" is a single FMA per element downstream.
+// that the apply kernel consumes, so "normalise" is a single FMA per element downstream.
 // Backward uses the same two-level shape: partial sums of du and du*x, a per-(n, group) finish producing the three
 // coefficients of  dx = a*du + b*x + c  per (n, channel), and a streaming apply.
 #include <stdlib.h>
@@ -94,26 +94,22 @@ __device__ __forceinline__ void block_fold(float (&a)[8], float (&b)[8], float* 
 
 // partial[n][c][chunk][2] = (sum x, sum x^2) over the chunk's voxels
 __global__ void __launch_bounds__(kT) k_gn_partial(const bf16* __restrict__ x, int cstride, float* __restrict__ partial, int C,
-                                                   int64_t V, int64_t vchunk, int sweep) {
+                                                   int64_t V, int64_t vchunk) {
   extern __shared__ float sm[];  // [rows][C][2]
   const int C8 = C / 8, rows = kT / C8;
   const int cg = threadIdx.x % C8, r = threadIdx.x / C8;
   const int n = blockIdx.y;
-  // sweep: the blocks of an image advance through it TOGETHER (block b takes voxel lanes b*rows + r of every stride of gridDim.x*rows
-  // voxels) instead of each block walking its own chunk: memory is touched front to back in time, so that the pass that follows can
-  // walk back to front and meet the lines this one touched last while they are still in the 256 MiB Infinity Cache (mi_gn_bwd)
-  const int64_t step = sweep ? (int64_t)gridDim.x * rows : rows;
-  const int64_t v0 = sweep ? (int64_t)blockIdx.x * rows : blockIdx.x * vchunk, v1 = sweep ? V : ((v0 + vchunk < V) ? v0 + vchunk : V);
+  const int64_t v0 = blockIdx.x * vchunk, v1 = (v0 + vchunk < V) ? v0 + vchunk : V;
   float s[8], q[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s[j] = q[j] = 0.f;
   if (r < rows) {
     const bf16* base = x + (int64_t)n * V * cstride + cg * 8;
-    for (int64_t v = v0 + r; v < v1; v += 4 * step) {  // 4 independent 16-byte loads in flight per lane
+    for (int64_t v = v0 + r; v < v1; v += 4 * rows) {  // 4 independent 16-byte loads in flight per lane
       u32x4 raw[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        int64_t vk = v + (int64_t)k * step;
+        int64_t vk = v + (int64_t)k * rows;
         u32x4 z = {0u, 0u, 0u, 0u};
         raw[k] = vk < v1 ? *(const u32x4*)(base + vk * cstride) : z;
       }
@@ -199,23 +195,20 @@ __global__ void __launch_bounds__(256) k_gn_finalize(const float* __restrict__ p
 // are in flight per lane.
 template <int ACT>
 __global__ void __launch_bounds__(kT) k_gn_apply(const bf16* __restrict__ x, int xcs, const float* __restrict__ scale_shift,
-                                                 bf16* __restrict__ y, int ycs, int C8, int64_t V, int rev) {
+                                                 bf16* __restrict__ y, int ycs, int C8, int64_t V) {
   const int C = C8 * 8;
   const int tid = blockIdx.x * kT + threadIdx.x;
   const int cg = tid % C8, R = gridDim.x * kT / C8;
   const int64_t n = blockIdx.y;
   float sc[8], sh[8];
   load_ss(scale_shift + n * C * 2, cg * 8, sc, sh);
-  // rev: walk the image back to front (voxel V-1-v): right behind a statistics pass that swept it front to back, the lines that
-  // pass touched last are met first, while they are still in the Infinity Cache
-  const bf16* xb = x + n * V * xcs + cg * 8 + (rev ? (V - 1) * xcs : 0);
-  bf16* yb = y + n * V * ycs + cg * 8 + (rev ? (V - 1) * ycs : 0);
-  const int64_t xs = rev ? -(int64_t)xcs : xcs, ys = rev ? -(int64_t)ycs : ycs;
+  const bf16* xb = x + n * V * xcs + cg * 8;
+  bf16* yb = y + n * V * ycs + cg * 8;
   for (int64_t v = tid / C8; v < V; v += 4 * (int64_t)R) {
     u32x4 raw[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (v + k * (int64_t)R < V) raw[k] = *(const u32x4*)(xb + (v + k * (int64_t)R) * xs);
+      if (v + k * (int64_t)R < V) raw[k] = *(const u32x4*)(xb + (v + k * (int64_t)R) * xcs);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       if (v + k * (int64_t)R >= V) break;
@@ -225,7 +218,7 @@ __global__ void __launch_bounds__(kT) k_gn_apply(const bf16* __restrict__ x, int
         float u = f.v[j] * sc[j] + sh[j];
         f.v[j] = act_f<ACT>(u);
       }
-      *(u32x4*)(yb + (v + k * (int64_t)R) * ys) = pack8(f);
+      *(u32x4*)(yb + (v + k * (int64_t)R) * ycs) = pack8(f);
     }
   }
 }
@@ -234,13 +227,12 @@ __global__ void __launch_bounds__(kT) k_gn_apply(const bf16* __restrict__ x, int
 template <int ACT>
 __global__ void __launch_bounds__(kT) k_gn_bwd_partial(const bf16* __restrict__ g, int gcs, const bf16* __restrict__ x, int xcs,
                                                        const float* __restrict__ scale_shift, float* __restrict__ partial, int C,
-                                                       int64_t V, int64_t vchunk, int sweep, double* __restrict__ sums64, int nrep) {
+                                                       int64_t V, int64_t vchunk, double* __restrict__ sums64, int nrep) {
   extern __shared__ float sm[];
   const int C8 = C / 8, rows = kT / C8;
   const int cg = threadIdx.x % C8, r = threadIdx.x / C8;
   const int n = blockIdx.y;
-  const int64_t step = sweep ? (int64_t)gridDim.x * rows : rows;  // (see k_gn_partial)
-  const int64_t v0 = sweep ? (int64_t)blockIdx.x * rows : blockIdx.x * vchunk, v1 = sweep ? V : ((v0 + vchunk < V) ? v0 + vchunk : V);
+  const int64_t v0 = blockIdx.x * vchunk, v1 = (v0 + vchunk < V) ? v0 + vchunk : V;
   float s1[8], s2[8], sc[8], sh[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) s1[j] = s2[j] = 0.f;
@@ -248,11 +240,11 @@ __global__ void __launch_bounds__(kT) k_gn_bwd_partial(const bf16* __restrict__ 
     load_ss(scale_shift + (int64_t)n * C * 2, cg * 8, sc, sh);
     const bf16* xb = x + (int64_t)n * V * xcs + cg * 8;
     const bf16* gb = g + (int64_t)n * V * gcs + cg * 8;
-    for (int64_t v = v0 + r; v < v1; v += 4 * step) {  // 8 independent 16-byte loads in flight per lane
+    for (int64_t v = v0 + r; v < v1; v += 4 * rows) {  // 8 independent 16-byte loads in flight per lane
       u32x4 rx[4], rg[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        int64_t vk = v + (int64_t)k * step;
+        int64_t vk = v + (int64_t)k * rows;
         u32x4 z = {0u, 0u, 0u, 0u};
         rx[k] = vk < v1 ? *(const u32x4*)(xb + vk * xcs) : z;
         rg[k] = vk < v1 ? *(const u32x4*)(gb + vk * gcs) : z;  // g = 0 beyond the chunk -> contributes nothing
@@ -356,16 +348,18 @@ __global__ void __launch_bounds__(256) k_gn_bwd_finalize(const float* __restrict
   }
 }
 
-// dx = a*du + b*x + c (+ add); grid as in k_gn_apply: 40 per-channel constants stay in registers
-template <int ACT, int U, bool NT>
+// dx = a*du + b*x + c (+ add); grid as in k_gn_apply: 40 per-channel constants stay in registers.  Two pieces in flight per stream;
+// the streams this pass reads for the last time (g, the pending gradient branches) and dx go past the caches (see mi_gn_bwd).
+template <int ACT>
 __global__ void __launch_bounds__(kT) k_gn_bwd_apply(const bf16* __restrict__ g, int gcs, const bf16* __restrict__ x, int xcs,
                                                      const float* __restrict__ scale_shift, const float* __restrict__ coef,
                                                      const bf16* __restrict__ add, int acs, const bf16* __restrict__ add2, int a2cs,
-                                                     bf16* __restrict__ dx, int dcs, int C8, int64_t V, int rev,
+                                                     bf16* __restrict__ dx, int dcs, int C8, int64_t V,
                                                      const double* __restrict__ sums64, const float* __restrict__ gamma,
                                                      const float* __restrict__ mean_rstd, int G, float* __restrict__ dgamma,
                                                      float* __restrict__ dbeta, int nrep) {
   extern __shared__ double ssum[];  // fused form only: this image's [C][2] sums, replicas folded in a fixed order
+  constexpr int U = 2;
   const int C = C8 * 8;
   const int tid = blockIdx.x * kT + threadIdx.x;
   const int cg = tid % C8, R = gridDim.x * kT / C8;
@@ -427,18 +421,18 @@ __global__ void __launch_bounds__(kT) k_gn_bwd_apply(const bf16* __restrict__ g,
     u32x4 rx[U], rg[U], ra[U], ra2[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
-      const int64_t vf = v + k * (int64_t)R, vk = rev ? V - 1 - vf : vf;  // rev: back to front (see k_gn_apply)
-      if (vf < V) {
+      const int64_t vk = v + k * (int64_t)R;
+      if (vk < V) {
         rx[k] = *(const u32x4*)(xb + vk * xcs);
-        rg[k] = NT ? __builtin_nontemporal_load((const u32x4*)(gb + vk * gcs)) : *(const u32x4*)(gb + vk * gcs);
-        if (ab) ra[k] = NT ? __builtin_nontemporal_load((const u32x4*)(ab + vk * acs)) : *(const u32x4*)(ab + vk * acs);
-        if (a2b) ra2[k] = NT ? __builtin_nontemporal_load((const u32x4*)(a2b + vk * a2cs)) : *(const u32x4*)(a2b + vk * a2cs);
+        rg[k] = __builtin_nontemporal_load((const u32x4*)(gb + vk * gcs));
+        if (ab) ra[k] = __builtin_nontemporal_load((const u32x4*)(ab + vk * acs));
+        if (a2b) ra2[k] = __builtin_nontemporal_load((const u32x4*)(a2b + vk * a2cs));
       }
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
-      const int64_t vf = v + k * (int64_t)R, vk = rev ? V - 1 - vf : vf;
-      if (vf >= V) break;
+      const int64_t vk = v + k * (int64_t)R;
+      if (vk >= V) break;
       F8 fx = unpack8(rx[k]), fg = unpack8(rg[k]), o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
@@ -456,8 +450,7 @@ __global__ void __launch_bounds__(kT) k_gn_bwd_apply(const bf16* __restrict__ g,
 #pragma unroll
         for (int j = 0; j < 8; ++j) o.v[j] += fa.v[j];
       }
-      if (NT) __builtin_nontemporal_store(pack8(o), (u32x4*)(db + vk * dcs));
-      else *(u32x4*)(db + vk * dcs) = pack8(o);
+      __builtin_nontemporal_store(pack8(o), (u32x4*)(db + vk * dcs));
     }
   }
 }
@@ -484,12 +477,11 @@ inline int64_t pick_vchunk(int64_t V) {
   if (vc < 16) vc = 16;
   return vc;
 }
-// The kernels' sweep / reverse flag is always 0: every block walks its own chunk, both passes front to back.  With the flag set the
-// statistics passes sweep an image front to back with all blocks abreast and the apply passes walk it back to front, so that they meet
-// the lines the partial pass touched last while they could still be in the 256 MiB Infinity Cache.  Measured (round 3,
-// profiles/r03b_ab_gn_sweep.log, same box, interleaved): 24.20 ms/step without, 24.25 with the backward's passes swept, 24.26 with the
-// forward apply pass reversed too; mi_gn_bwd at 32 ch x 128^3 back to back: 139 us vs 146.  The two passes of a 268 MB working set gain
-// nothing from the order.
+// Every block walks its own chunk and both passes of a norm go front to back.  Measured against that (round 3,
+// profiles/r03b_ab_gn_sweep.log, same box, interleaved): the statistics passes sweeping an image with all blocks abreast and the apply
+// passes walking it back to front, to meet the lines touched last while they could still be in the 256 MiB Infinity Cache --
+// 24.20 ms/step without, 24.25 with the backward's passes swept, 24.26 with the forward apply reversed too; mi_gn_bwd at
+// 32 ch x 128^3: 139 us vs 146.  The two passes of a 268 MB working set gain nothing from the order; that form is gone.
 inline bool bad_c(int C, int G) { return C <= 0 || (C & 7) || C > 2048 || G <= 0 || C % G != 0; }
 
 // ---- small tensors (the 16^3 level of the C4 net; 2-D nets): statistics -> coefficients -> apply in ONE launch.  Three launches of
@@ -606,7 +598,7 @@ int mi_gn_stats(const void* x, int x_cstride, int N, int64_t V, int C, int G, fl
   int chunks = (int)((V + vc - 1) / vc);
   int rows = kT / (C / 8);
   hipLaunchKernelGGL(k_gn_partial, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)x, x_cstride,
-                     (float*)workspace, C, V, vc, 0);
+                     (float*)workspace, C, V, vc);
   hipLaunchKernelGGL(k_gn_finalize, dim3(N * G), dim3(256), 0, st, (const float*)workspace, chunks, C, (const float*)nullptr, 0, C, G, V, eps,
                      gamma, beta, scale_shift, mean_rstd);
   MI_CHECK_LAUNCH();
@@ -629,7 +621,7 @@ int mi_gn_apply(const void* x, int x_cstride, const float* scale_shift, void* y,
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
   if (silu < 0 || silu > 2) return MI_ERR_BAD_ARG;  // activation code: 0 none, 1 SiLU, 2 LeakyReLU(0.2)
   auto k = silu == 1 ? k_gn_apply<1> : (silu == 2 ? k_gn_apply<2> : k_gn_apply<0>);
-  hipLaunchKernelGGL(k, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)x, x_cstride, scale_shift, (bf16*)y, y_cstride, C / 8, V, 0);
+  hipLaunchKernelGGL(k, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)x, x_cstride, scale_shift, (bf16*)y, y_cstride, C / 8, V);
   MI_CHECK_LAUNCH();
   return 0;
 }
@@ -662,18 +654,17 @@ int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N,
   if (silu < 0 || silu > 2) return MI_ERR_BAD_ARG;
   auto kp = silu == 1 ? k_gn_bwd_partial<1> : (silu == 2 ? k_gn_bwd_partial<2> : k_gn_bwd_partial<0>);
   hipLaunchKernelGGL(kp, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)g, g_cstride, (const bf16*)x,
-                     x_cstride, scale_shift, (float*)workspace, C, V, vc, 0, (double*)nullptr, 1);
+                     x_cstride, scale_shift, (float*)workspace, C, V, vc, (double*)nullptr, 1);
   hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(N * G), dim3(256), sizeof(float) * 2 * (size_t)(C / G), st, (const float*)workspace, chunks, C,
                      G, V, gamma, mean_rstd, coef, dgamma, dbeta);
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
-  // k_gn_bwd_apply<ACT, 2, true>: 2 pieces in flight per stream, non-temporal loads of the streams this pass reads for the last time (g,
-  // the pending gradient branches) and non-temporal stores of dx.  Measured round 3, same box, interleaved
-  // (profiles/r03i_ab_gn_variant.log): 22.96 ms/step with <2, false>, 23.03 with <4, false>, 22.75 with <2, true>, 22.87 with <4, true>;
-  // mi_gn_bwd at 32 ch x 128^3 back to back 132.8 / 142.0 / 124.4 / 129.8 us.  The same hints on the forward apply pass and on the
-  // backward's partial pass measured within noise (profiles/r03i_ab_gn_nt2.log) and were not kept.
-  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
+  // k_gn_bwd_apply keeps 2 pieces in flight per stream and uses non-temporal loads (g, the pending gradient branches) and stores (dx).
+  // Measured round 3, same box, interleaved (profiles/r03i_ab_gn_variant.log), pieces in flight / non-temporal: 22.96 ms/step with 2 / no,
+  // 23.03 with 4 / no, 22.75 with 2 / yes (what ships), 22.87 with 4 / yes; mi_gn_bwd at 32 ch x 128^3 132.8 / 142.0 / 124.4 / 129.8 us.
+  // The same hints on the forward apply pass and on the backward's partial pass measured within noise (profiles/r03i_ab_gn_nt2.log).
+  auto ka = silu == 1 ? k_gn_bwd_apply<1> : (silu == 2 ? k_gn_bwd_apply<2> : k_gn_bwd_apply<0>);
   hipLaunchKernelGGL(ka, dim3((int)grid, N), dim3(kT), 0, st, (const bf16*)g, g_cstride, (const bf16*)x, x_cstride, scale_shift, coef,
-                     (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride, C / 8, V, 0,
+                     (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride, C / 8, V,
                      (const double*)nullptr, (const float*)nullptr, (const float*)nullptr, G, (float*)nullptr, (float*)nullptr, 1);
   MI_CHECK_LAUNCH();
   return 0;
@@ -694,12 +685,12 @@ int mi_gn_bwd_fused(const void* g, int g_cstride, const void* x, int x_cstride, 
   nrep = nrep < 1 ? 1 : (nrep > MI_GN_FUSED_REPLICAS ? MI_GN_FUSED_REPLICAS : nrep);
   auto kp = silu == 1 ? k_gn_bwd_partial<1> : (silu == 2 ? k_gn_bwd_partial<2> : k_gn_bwd_partial<0>);
   hipLaunchKernelGGL(kp, dim3(chunks, N), dim3(kT), sizeof(float) * (size_t)rows * C * 2, st, (const bf16*)g, g_cstride, (const bf16*)x,
-                     x_cstride, scale_shift, (float*)nullptr, C, V, vc, 0, sums_zeroed, nrep);
+                     x_cstride, scale_shift, (float*)nullptr, C, V, vc, sums_zeroed, nrep);
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
-  auto ka = silu == 1 ? k_gn_bwd_apply<1, 2, true> : (silu == 2 ? k_gn_bwd_apply<2, 2, true> : k_gn_bwd_apply<0, 2, true>);
+  auto ka = silu == 1 ? k_gn_bwd_apply<1> : (silu == 2 ? k_gn_bwd_apply<2> : k_gn_bwd_apply<0>);
   hipLaunchKernelGGL(ka, dim3((int)grid, N), dim3(kT), sizeof(double) * 2 * (size_t)C, st, (const bf16*)g, g_cstride, (const bf16*)x, x_cstride,
                      scale_shift, (const float*)nullptr, (const bf16*)add, add_cstride, (const bf16*)add2, add2_cstride, (bf16*)dx, dx_cstride,
-                     C / 8, V, 0, (const double*)sums_zeroed, gamma, mean_rstd, G, dgamma, dbeta, nrep);
+                     C / 8, V, (const double*)sums_zeroed, gamma, mean_rstd, G, dgamma, dbeta, nrep);
   MI_CHECK_LAUNCH();
   return 0;
 }

@@ -147,11 +147,6 @@ __global__ void __launch_bounds__(256) k_swap(f32x4* a, f32x4* b, int64_t n4, fl
     bt[threadIdx.x] = x;
   }
 }
-__global__ void __launch_bounds__(256) k_scale_by_clip(float* g, int64_t n, const float* sumsq, float max_norm) {
-  float c = max_norm / (sqrtf(*sumsq) + 1e-6f);
-  c = c < 1.f ? c : 1.f;
-  for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) g[i] *= c;
-}
 
 }  // namespace
 
@@ -233,15 +228,6 @@ int mi_axpy_f32(float* y, const float* x, float alpha, int64_t n, hipStream_t st
   int grid = (int)((n4 + 255) / 256);
   grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
   hipLaunchKernelGGL(k_axpy, dim3(grid), dim3(256), 0, st, (f32x4*)y, (const f32x4*)x, alpha, n4, y + n4 * 4, x + n4 * 4, (int)(n - n4 * 4));
-  MI_CHECK_LAUNCH();
-  return 0;
-}
-
-int mi_clip_grad_by_norm(float* grad, int64_t n, const float* grad_sumsq, float max_norm, hipStream_t st) {
-  if (n <= 0) return MI_ERR_BAD_ARG;
-  int grid = (int)((n + 255) / 256);
-  grid = grid > 4096 ? 4096 : grid;
-  hipLaunchKernelGGL(k_scale_by_clip, dim3(grid), dim3(256), 0, st, grad, n, grad_sumsq, max_norm);
   MI_CHECK_LAUNCH();
   return 0;
 }

@@ -283,7 +283,7 @@ class ConvPlan:
         """Splits of the tile range the tiled weight-gradient kernels of this plan run with (tests)."""
         return int(_lib.call_raw("mi_conv_plan_wgrad_splits", self.handle))
 
-    def fwd(self, x, st: GNStats | None = None, silu=False, addvec=None, res=None, out=None, want_sums=False):
+    def fwd(self, x, addvec=None, res=None, out=None, want_sums=False):
         """out: optional destination, a channel-slice view [N, D, H, W, Cout] of a wider channels-last buffer (the conv writes
         straight into the skip-concat buffer of its consumer instead of being copied there).  want_sums: also return the
         ChannelSums of y when this plan's kernel can emit them (else None): (y, sums)."""
@@ -299,10 +299,10 @@ class ConvPlan:
             assert addvec.shape == (n, self.cout) and addvec.stride(1) == 1
             av_stride = addvec.stride(0)
         sums = None
-        if want_sums and FUSE_GN_STATS and st is None and self.stats_chunks > 0 and (_cs(x) % 8 == 0 or (self.cin == 1 and res is None)):
+        if want_sums and FUSE_GN_STATS and self.stats_chunks > 0 and (_cs(x) % 8 == 0 or (self.cin == 1 and res is None)):
             sums = ChannelSums(torch.empty((n, self.cout, self.stats_chunks, 2), dtype=F32, device=x.device), self.stats_chunks, self.cout)
-        call("mi_conv_fwd", self.handle, ptr(x), _cs(x), ptr(st.scale_shift) if st is not None else None, int(silu), ptr(addvec), av_stride,
-             ptr(res), _cs(res) if res is not None else 0, ptr(y), _cs(y), ptr(sums.partial) if sums is not None else None)
+        call("mi_conv_fwd", self.handle, ptr(x), _cs(x), ptr(addvec), av_stride, ptr(res), _cs(res) if res is not None else 0, ptr(y), _cs(y),
+             ptr(sums.partial) if sums is not None else None)
         return (y, sums) if want_sums else y
 
     def dgrad(self, dy):
@@ -311,7 +311,7 @@ class ConvPlan:
         call("mi_conv_dgrad", self.handle, ptr(dy), _cs(dy), ptr(dx), self.cin)
         return dx
 
-    def wgrad(self, x, dy, dweight_f32, st: GNStats | None = None, silu=False, colsum=None):
+    def wgrad(self, x, dy, dweight_f32, colsum=None):
         """dweight += wgrad; colsum (optional fp32) += column sums of dy: an [N, Cout] view (row pitch honoured) receives them
         per image, a [Cout] vector their sum over the batch (the bias gradient)."""
         assert dweight_f32.dtype == F32 and dweight_f32.is_contiguous()
@@ -323,8 +323,7 @@ class ConvPlan:
                 cs_stride = colsum.stride(0)
             else:
                 assert colsum.shape == (self.cout,)
-        call("mi_conv_wgrad", self.handle, ptr(x), _cs(x), ptr(st.scale_shift) if st is not None else None, int(silu), ptr(dy), _cs(dy),
-             ptr(dweight_f32), ptr(colsum), cs_stride)
+        call("mi_conv_wgrad", self.handle, ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(dweight_f32), ptr(colsum), cs_stride)
 
 
 class UpConvPlan(ConvPlan):
@@ -502,11 +501,4 @@ def cast_bf16(x_f32):
     assert x_f32.is_contiguous() and x_f32.dtype == F32
     out = torch.empty(x_f32.shape, dtype=BF16, device=x_f32.device)
     call("mi_cast_f32_to_bf16", ptr(x_f32), ptr(out), x_f32.numel())
-    return out
-
-
-def cast_f32(x_bf16, out=None, accumulate=False):
-    if out is None:
-        out = torch.empty(x_bf16.shape, dtype=F32, device=x_bf16.device)
-    call("mi_cast_bf16_to_f32", ptr(x_bf16), ptr(out), x_bf16.numel(), int(accumulate))
     return out

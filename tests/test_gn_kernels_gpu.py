@@ -32,7 +32,7 @@ def lib():
 
 # ----------------------------------------------------------------------------------------------------------- launch geometry
 def apply_trips(n, c, v, slots):
-    """The grid-stride loop of k_gn_apply (slots = 4) and k_gn_bwd_apply (slots = U = 2, the default variant), restated from
+    """The grid-stride loop of k_gn_apply (slots = 4) and k_gn_bwd_apply (slots = 2, its pieces in flight per stream), restated from
     apply_grid() in csrc/groupnorm.hip: ~16 blocks per CU over the batch (at least 64), ceil(V * C8 / 256) below that, then
     trimmed so that grid * 256 is a multiple of C8.  A trip covers slots * R voxels, R = grid * 256 / C8.
     Returns (R, full trips, voxels in the ragged last trip)."""

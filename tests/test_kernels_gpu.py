@@ -436,8 +436,9 @@ def test_conv27_at_size_vs_fp32_reference(ops, c):
         check(got[..., 1], (yf * yf).sum(dim=(1, 2, 3)), 1e-3, "emitted channel sums of squares")
 
 
-def test_conv_fused_prologue_epilogue(ops):
-    """GroupNorm-affine + SiLU prologue, per-sample add vector (bias + temb) and residual in the epilogue."""
+def test_conv_norm_pass_epilogue(ops):
+    """GroupNorm + SiLU as the pass in front of the conv (the engine's order), per-sample add vector (bias + temb) and residual in the
+    conv's epilogue."""
     n, cin, cout, dims = 2, 64, 32, (4, 8, 8)
     x = rnd(n, cin, *dims, scale=1.3) + 0.2
     x = x.bfloat16().float()
@@ -454,10 +455,11 @@ def test_conv_fused_prologue_epilogue(ops):
     plan.pack(w.to(dev))
     xc = cl(x)
     st = ops.gn_stats(xc, 32, 1e-6, gamma.to(dev), beta.to(dev))
-    check(cf(plan.fwd(xc, st, True, addvec=addv.to(dev), res=cl(res))), y.detach(), 1e-2, "fused fwd")
+    xin = ops.gn_apply(xc, st, True)
+    check(cf(plan.fwd(xin, addvec=addv.to(dev), res=cl(res))), y.detach(), 1e-2, "norm pass + conv fwd")
     dw = torch.zeros_like(w).to(dev)
-    plan.wgrad(xc, cl(g), dw, st, True)
-    check(dw.cpu(), wr.grad, 1e-2, "fused wgrad")
+    plan.wgrad(xin, cl(g), dw)
+    check(dw.cpu(), wr.grad, 1e-2, "wgrad against the activated input")
     check(cf(plan.dgrad(cl(g))), act.grad, 1e-2, "dgrad wrt activated input")
 
 

@@ -33,8 +33,8 @@ def wrap(mod, name):
 for n in ("gn_stats", "gn_stats_from_sums", "gn_apply", "gn_bwd", "add", "upsample_nearest", "upsample_nearest_bwd"):
     wrap(ops, n)
 _of = ops.ConvPlan.fwd
-def fwd_dbg(self, x, st=None, silu=False, addvec=None, res=None, out=None, want_sums=False):
-    r = _of(self, x, st, silu, addvec=addvec, res=res, out=out, want_sums=want_sums)
+def fwd_dbg(self, x, addvec=None, res=None, out=None, want_sums=False):
+    r = _of(self, x, addvec=addvec, res=res, out=out, want_sums=want_sums)
     y = r[0] if isinstance(r, tuple) else r
     if first[0] is None and bad(y):
         first[0] = True
