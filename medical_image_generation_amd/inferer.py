@@ -14,6 +14,12 @@ timestep is a device scalar the embedding and update kernels read, so all 1000 s
 Few-step sampling and image-to-noise inversion go through `DDIMScheduler` (third-party `generative` as well, Song et al. 2021 as
 upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED): the same loop with `mi_ddim_step` as the update kernel,
 which reads row i of a per-run table of step constants, so step count, eta and direction change without a new capture.
+
+Class-conditional models sample with `class_labels=`.  Classifier-free guidance (`guidance_scale=`; Ho & Salimans 2022 -- not part of the
+reference; PARITY UNPINNED): every step is ONE forward at batch 2N -- the conditional half [0, N) and the null half [N, 2N) -- and one
+`mi_ddpm_step_guided` / `mi_ddim_step_guided` launch that forms m = m_uncond + w (m_cond - m_uncond) and continues with the unguided
+arithmetic.  Null means zeros for the cross-attention context and the concatenated condition channels, and `null_class` for the
+class route -- what trainer.DDPMTrainer(..., null_class=).step(..., drop) trains.  w is a device scalar: one graph serves every scale.
 """
 from __future__ import annotations
 
@@ -200,11 +206,14 @@ class DDIMScheduler:
 class _Loop:
     """One captured denoising step, replayed over scheduler.timesteps."""
 
-    def __init__(self, model, scheduler, shape, device, cond_channels=0, context_shape=None):
+    def __init__(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False):
         """cond_channels: channels of a mode="concat" conditioning tensor that sit, un-noised, behind the sample's channels in the model
-        input; context_shape: (tokens, cross_attention_dim) of a mode="crossattn" conditioning."""
+        input; context_shape: (tokens, cross_attention_dim) of a mode="crossattn" conditioning; labels: the model reads class labels;
+        guided: classifier-free guidance -- the model runs at batch 2N (condition, then null condition), the sample stays at batch N."""
         self.m, self.sch = model, scheduler
         n, c = shape[0], shape[1]
+        self.guided = bool(guided)
+        nb = 2 * n if self.guided else n  # the model's batch
         sp = tuple(shape[2:])
         self.v = 1
         for s in sp:
@@ -213,12 +222,14 @@ class _Loop:
         self.n, self.c = n, c
         self.x = torch.empty(shape, dtype=F32, device=device)                    # the sample, fp32 NC[D]HW
         self.cc = int(cond_channels)
-        self.x_cl = torch.empty((n,) + dims + (c + self.cc,), dtype=torch.bfloat16, device=device)  # ... as the model reads it (+ condition)
-        self.ctx = None if context_shape is None else torch.empty((n * context_shape[0], context_shape[1]), dtype=torch.bfloat16, device=device)
+        self.x_cl = torch.empty((nb,) + dims + (c + self.cc,), dtype=torch.bfloat16, device=device)  # ... as the model reads it (+ condition)
+        self.ctx = None if context_shape is None else torch.empty((nb * context_shape[0], context_shape[1]), dtype=torch.bfloat16, device=device)
+        self.labels = torch.zeros(nb, dtype=torch.int64, device=device) if labels else None
+        self.w = torch.ones(1, dtype=F32, device=device) if self.guided else None  # the guidance scale the guided update kernel reads
         self.z = torch.empty(shape, dtype=F32, device=device)
         self.ddim = isinstance(scheduler, DDIMScheduler)
         self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its table with: t (DDPM), step i (DDIM)
-        self.tn = torch.zeros(n, dtype=torch.int64, device=device)  # the timestep the model reads
+        self.tn = torch.zeros(nb, dtype=torch.int64, device=device)  # the timestep the model reads
         self.coef = scheduler.coefficients(device)
         self.arena = model.arena(device)
         self.graph = None
@@ -227,23 +238,43 @@ class _Loop:
 
     def _step(self):
         ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
-        eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, context=self.ctx)
-        call("mi_ddim_step" if self.ddim else "mi_ddpm_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.x_cl),
-             self.c + self.cc, self.n, self.c, self.v, int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0))
+        eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, class_labels=self.labels, context=self.ctx)
+        flags = int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0)
+        if self.guided:  # eps holds both branches: the kernel combines them, steps, and rewrites the sample channels of both halves
+            call("mi_ddim_step_guided" if self.ddim else "mi_ddpm_step_guided", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t),
+                 ptr(self.w), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, flags)
+        else:
+            call("mi_ddim_step" if self.ddim else "mi_ddpm_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.x_cl),
+                 self.c + self.cc, self.n, self.c, self.v, flags)
 
     def _load(self, x):
         """x (fp32 NC[D]HW) -> the sample channels of the model input (the condition channels behind them stay)."""
         self.x.copy_(x)
-        self.x_cl[..., :self.c].copy_(ops.to_channels_last(self.x))
+        x_cl = ops.to_channels_last(self.x)
+        for h in range(2 if self.guided else 1):
+            self.x_cl[h * self.n:(h + 1) * self.n, ..., :self.c].copy_(x_cl)
 
-    def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None, eta=0.0, reverse=False):
-        """eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps."""
+    def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None, eta=0.0, reverse=False,
+            class_labels=None, guidance_scale=None, null_class=None):
+        """eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps.
+        class_labels (int64 [N]), guidance_scale, null_class: what the loop was built for (labels / guided); filled before any step."""
         if self.m._arena is not self.arena:  # the module moved (.to / .cuda): plans and graph point at the old buffers -> start over
             self.arena, self.graph, self.keys, self._pinned = self.m.arena(self.x.device), None, (), None
+        n = self.n
         if self.cc:  # mode="concat": model_input = cat([image, conditioning], dim=1) at every step; written once, the steps rewrite `image`
-            self.x_cl[..., self.c:].copy_(ops.to_channels_last(conditioning))
+            self.x_cl[:n, ..., self.c:].copy_(ops.to_channels_last(conditioning))
         elif self.ctx is not None:  # mode="crossattn": the context token matrix is a constant of the loop
-            self.ctx.copy_(ops.cast_bf16(conditioning.contiguous().reshape(-1, conditioning.shape[2])))
+            self.ctx[:n * conditioning.shape[1]].copy_(ops.cast_bf16(conditioning.contiguous().reshape(-1, conditioning.shape[2])))
+        if self.labels is not None:
+            self.labels[:n].copy_(class_labels)
+        if self.guided:  # the null half: zero condition channels, zero context tokens, the null class
+            if self.cc:
+                self.x_cl[n:, ..., self.c:].zero_()
+            elif self.ctx is not None:
+                self.ctx[n * conditioning.shape[1]:].zero_()
+            if self.labels is not None:
+                self.labels[n:].fill_(null_class)
+            self.w.fill_(float(guidance_scale))
         self._load(input_noise)
         steps = [int(t) for t in self.sch.timesteps]
         if self.ddim:  # the rows of THIS run, written into the table the (possibly already captured) step reads, before any step runs
@@ -295,10 +326,10 @@ class DiffusionInferer:
         self.scheduler = scheduler
         self._loops = {}
 
-    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None):
-        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape)
+    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False):
+        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape, bool(guided), bool(labels))
         if key not in self._loops:
-            self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape)
+            self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape, guided, labels)
         return self._loops[key]
 
     @staticmethod
@@ -317,8 +348,9 @@ class DiffusionInferer:
             noisy, condition = torch.cat([noisy, condition.to(noisy.dtype)], dim=1), None
         return diffusion_model(x=noisy, timesteps=timesteps, context=condition)
 
-    def _conditioning(self, x, diffusion_model, conditioning, mode):
-        """The checks of a sample / invert call -> (conditioning as fp32 on x's device, concat channels, cross-attention context shape)."""
+    def _conditioning(self, x, diffusion_model, conditioning, mode, class_labels=None, guidance_scale=None, null_class=None):
+        """The checks of a sample / invert call -> (conditioning as fp32 on x's device, concat channels, cross-attention context shape,
+        class labels as int64 [N] on x's device or None)."""
         self._check_mode(mode)
         if not x.is_cuda:
             raise RuntimeError("medical_image_generation_amd runs on MI355X only: move the inputs to 'cuda'")
@@ -341,16 +373,35 @@ class DiffusionInferer:
         if x.shape[1] + cc != diffusion_model.in_channels:
             raise ValueError(f"Input number of channels ({x.shape[1] + cc}) is not equal to expected number of channels "
                              f"({diffusion_model.in_channels})")
-        return conditioning, cc, ctx_shape
+        nce = getattr(diffusion_model, "num_class_embeds", None)
+        if (class_labels is None) != (nce is None):
+            raise ValueError("class_labels should be provided exactly when the model has num_class_embeds")
+        if class_labels is not None:  # the kernels index the embedding table with them: nn.Embedding's range check, on the host
+            class_labels = torch.as_tensor(class_labels).to(device=x.device, dtype=torch.int64).contiguous()
+            if class_labels.shape != (x.shape[0],) or int(class_labels.min()) < 0 or int(class_labels.max()) >= nce:
+                raise ValueError(f"class_labels must hold one index in [0, {nce}) per sample")
+        if guidance_scale is not None:
+            if conditioning is None and class_labels is None:
+                raise ValueError("guidance_scale: there is no conditioning to guide with (no conditioning=, no class_labels=)")
+            if class_labels is not None and (null_class is None or not 0 <= int(null_class) < nce):
+                raise ValueError(f"guidance on a class-conditional model needs null_class= in [0, {nce}): the label of the unconditional branch")
+        return conditioning, cc, ctx_shape, class_labels
 
     @torch.no_grad()
     def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
-               mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0):
+               mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
+               guidance_scale=None, null_class=None):
         """conditioning with mode="concat": fp32 NC'[D]HW, model_input = cat([image, conditioning], dim=1) at every step; with
         mode="crossattn": fp32 [N, tokens, cross_attention_dim], the model's `context` (train_ldm.py:349-365 passes neither).
         noises: optional sequence with the z of every step (tests pin them); generator: torch generator for the per-step noise.
-        eta: the noise scale of a DDIMScheduler (0 = deterministic; no per-step noise is drawn); other schedulers ignore it."""
-        conditioning, cc, ctx_shape = self._conditioning(input_noise, diffusion_model, conditioning, mode)
+        eta: the noise scale of a DDIMScheduler (0 = deterministic; no per-step noise is drawn); other schedulers ignore it.
+        class_labels: int64 [N], for a model built with num_class_embeds.
+        guidance_scale: a float w selects classifier-free guidance (not part of the reference; PARITY UNPINNED): the model output of
+        every step is m_uncond + w (m_cond - m_uncond), from one forward at batch 2N whose second half carries the null condition --
+        zero context tokens, zero condition channels, and `null_class` (required with class_labels) as the label.  w = 1 is the
+        conditional model, w = 0 the unconditional one; the scale is a device scalar, so all scales share one captured graph."""
+        conditioning, cc, ctx_shape, class_labels = self._conditioning(input_noise, diffusion_model, conditioning, mode, class_labels,
+                                                                       guidance_scale, null_class)
         scheduler = scheduler or self.scheduler
         inter = []
 
@@ -358,21 +409,26 @@ class DiffusionInferer:
             if save_intermediates and t % intermediate_steps == 0:
                 inter.append(x.clone())
 
-        loop = self._loop(diffusion_model, scheduler, input_noise.shape, input_noise.device, cc, ctx_shape)
+        loop = self._loop(diffusion_model, scheduler, input_noise.shape, input_noise.device, cc, ctx_shape, guidance_scale is not None,
+                          class_labels is not None)
         image = loop.run(input_noise.float(), noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning,
-                         eta=eta)
+                         eta=eta, class_labels=class_labels, guidance_scale=guidance_scale, null_class=null_class)
         return (image, inter) if save_intermediates else image
 
     @torch.no_grad()
-    def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True):
+    def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True, class_labels=None,
+               guidance_scale=None, null_class=None):
         """Image-to-noise DDIM inversion: DDIMScheduler.reversed_step over ascending timesteps in the fused loop of `sample` (same
-        captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler."""
+        captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler.
+        class_labels, guidance_scale, null_class: as in `sample`."""
         scheduler = scheduler or self.scheduler
         if not isinstance(scheduler, DDIMScheduler):
             raise TypeError(f"invert needs a DDIMScheduler (reversed_step), not {type(scheduler).__name__}")
-        conditioning, cc, ctx_shape = self._conditioning(image, diffusion_model, conditioning, mode)
-        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape)
-        return loop.run(image.float(), use_graph=use_graph, conditioning=conditioning, reverse=True)
+        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
+                                                                       null_class)
+        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None, class_labels is not None)
+        return loop.run(image.float(), use_graph=use_graph, conditioning=conditioning, reverse=True, class_labels=class_labels,
+                        guidance_scale=guidance_scale, null_class=null_class)
 
 
 class LatentDiffusionInferer(DiffusionInferer):
@@ -392,9 +448,11 @@ class LatentDiffusionInferer(DiffusionInferer):
 
     @torch.no_grad()
     def sample(self, input_noise, autoencoder_model, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100,
-               conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0):
+               conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
+               guidance_scale=None, null_class=None):
         out = super().sample(input_noise, diffusion_model, scheduler, save_intermediates, intermediate_steps, conditioning, mode, verbose,
-                             noises=noises, generator=generator, use_graph=use_graph, eta=eta)
+                             noises=noises, generator=generator, use_graph=use_graph, eta=eta, class_labels=class_labels,
+                             guidance_scale=guidance_scale, null_class=null_class)
         latent, inter = out if save_intermediates else (out, None)
         image = autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
         if save_intermediates:
@@ -402,7 +460,8 @@ class LatentDiffusionInferer(DiffusionInferer):
         return image
 
     @torch.no_grad()
-    def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True):
+    def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True,
+               class_labels=None, guidance_scale=None, null_class=None):
         """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor)."""
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
-        return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph)
+        return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class)

@@ -99,6 +99,14 @@ def kl_weight_from_mean(kl_mean: float) -> float:
     return 0.001 / 10.0 ** math.floor(math.log10(kl_mean))
 
 
+def draw_drop(n, p, generator=None, device="cuda"):
+    """A condition-dropout mask for classifier-free guidance training: torch.bool [n] on the device, True with probability p (Ho &
+    Salimans 2022 train with p around 0.1 - 0.2).  `generator`: a torch generator of `device`.  Pass it as the trainers' `drop`."""
+    if not 0.0 <= float(p) <= 1.0:
+        raise ValueError(f"the drop probability must lie in [0, 1], got {p}")
+    return torch.rand(int(n), device=device, generator=generator) < float(p)
+
+
 class DDPMSchedule:
     """alphas_cumprod of generative's DDPMScheduler (closed form; see oracle/step.py for provenance)."""
 
@@ -478,23 +486,34 @@ class _ArenaTrainer:
 
 
 class DDPMTrainer(_ArenaTrainer):
-    """step(x0, noise, timesteps[, class_labels][, context=...][, condition=...]): x0/noise fp32 NCDHW, timesteps (and class_labels)
+    """step(x0, noise, timesteps[, class_labels][, context=...][, condition=...][, drop=...]): x0/noise fp32 NCDHW, timesteps (and class_labels)
     int64 [N]; context: fp32 [N, tokens, cross_attention_dim] for a net built with with_conditioning=True (the `context=` of
     DiffusionModelUNet.forward, UNet:1936-1944), a constant of the step like in forward().
 
     condition: channel-concatenation conditioning (the third-party inferer's `condition=..., mode="concat"`, the arguments of the call at
     train_ddpm.py:191; BASELINE configs[4] "label-channel conditioning"): fp32 NC'[D]HW, spatially like x0.  Only x0's channels are
     noised; the condition channels are written un-noised behind them -- model input = cat([noisy, condition], dim=1) with
-    in_channels = C + C' -- and the model predicts x0's C channels (out_channels = C), compared with x0's noise."""
+    in_channels = C + C' -- and the model predicts x0's C channels (out_channels = C), compared with x0's noise.
+
+    drop: condition dropout, the training half of classifier-free guidance (Ho & Salimans 2022; not part of the reference: PARITY
+    UNPINNED) -- torch.bool or torch.uint8 [N] on the device (`draw_drop`), non-zero = this sample trains unconditionally.  One mask drops
+    every conditioning the sample has, inside the step's kernels: its label becomes `null_class` (a row of the class embedding kept for
+    "no class", given to the constructor; forward and backward use it, so dropped samples train that row), its context rows and its
+    condition channels become zeros.  Like every input it is a static buffer of capture(): a new mask per replay needs no re-capture."""
 
     def __init__(self, model, lr=2e-5, optimizer="AdamW", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  schedule: DDPMSchedule | None = None, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, overlap=None,
-                 ema_decay=None, ema_warmup=False):
+                 ema_decay=None, ema_warmup=False, null_class=None):
         super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
                          grad_accumulate_step, overlap, ema_decay, ema_warmup)
         self.schedule = schedule or DDPMSchedule(device=self.device)
+        nce = getattr(model, "num_class_embeds", None)
+        if null_class is not None and (nce is None or not 0 <= int(null_class) < nce):
+            raise ValueError(f"null_class must be an index into the model's class embedding ([0, {nce})), got {null_class}"
+                             if nce is not None else "null_class is for a model with num_class_embeds")
+        self.null_class = None if null_class is None else int(null_class)
 
-    def _check_inputs(self, x0, noise, timesteps, class_labels, context, condition):
+    def _check_inputs(self, x0, noise, timesteps, class_labels, context, condition, drop=None):
         """Raw pointers go to the kernels: refuse anything they would misread instead of reading out of bounds.  -> channels of `condition`."""
         m = self.model
         if not (x0.is_cuda and noise.is_cuda and timesteps.is_cuda):
@@ -523,11 +542,31 @@ class DDPMTrainer(_ArenaTrainer):
             if not context.is_cuda or context.dtype != F32 or context.dim() != 3 or context.shape[0] != x0.shape[0] or \
                     context.shape[2] != m.cross_attention_dim:
                 raise ValueError(f"context must be a GPU fp32 tensor [batch, tokens, {m.cross_attention_dim}]")
+        self._check_drop(drop, x0, class_labels, context, condition)
         return cc
 
-    def _predict(self, grad_enabled, x0, noise, timesteps, class_labels, context, condition, cc):
+    def _check_drop(self, drop, x0, class_labels, context, condition):
+        """The condition-dropout mask against the batch (x0: any input that has the batch size and the device) and the conditioning."""
+        if drop is None:
+            return
+        if not isinstance(drop, torch.Tensor) or drop.dtype not in (torch.bool, torch.uint8):
+            raise ValueError("drop must be a torch.bool or torch.uint8 tensor (draw_drop)")
+        if drop.shape != (x0.shape[0],) or not drop.is_contiguous():
+            raise ValueError("drop must be a contiguous tensor of shape [N]")
+        if drop.device != x0.device:
+            raise ValueError("drop must live on the inputs' device")
+        if class_labels is None and context is None and condition is None:
+            raise ValueError("drop: this step has no conditioning to drop (no class_labels, context or condition)")
+        if class_labels is not None:
+            if self.null_class is None:
+                raise ValueError("drop on a class-conditional model needs the trainer's null_class=: the label dropped samples train")
+            if not class_labels.is_cuda or class_labels.dtype != torch.int64 or class_labels.shape != (x0.shape[0],) or \
+                    not class_labels.is_contiguous():  # mi_select_labels reads it raw
+                raise ValueError("class_labels must be a contiguous int64 GPU tensor of shape [N]")
+
+    def _predict(self, grad_enabled, x0, noise, timesteps, class_labels, context, condition, cc, drop=None):
         """q-sample -> UNet.  -> (ctx, pred, target, (n, v), the tensors its kernels read); target: the noise, or the velocity mi_qsample
-        wrote (v-prediction)."""
+        wrote (v-prediction).  drop: the checked condition-dropout mask or None (then exactly the launches of a step without one)."""
         m = self.model
         sd = m.spatial_dims
         n, c = x0.shape[0], x0.shape[1]
@@ -537,34 +576,49 @@ class DDPMTrainer(_ArenaTrainer):
         x_t = torch.empty((n,) + dims + (c + cc,), dtype=torch.bfloat16, device=x0.device)
         vpred = self.schedule.prediction_type == "v_prediction"  # target = scheduler.get_velocity(x0, noise, t), T-LDM:163-165
         target = torch.empty_like(noise) if vpred else noise
-        call("mi_qsample", ptr(x0), ptr(noise), ptr(self.schedule.sqrt_acp), ptr(self.schedule.sqrt_1macp), ptr(timesteps), ptr(condition), cc,
-             ptr(x_t), ptr(target) if vpred else None, n, c, v, self.schedule.num_train_timesteps)
+        mask = None if drop is None else drop.view(torch.uint8)  # (bool and uint8 share the byte layout the kernels read)
+        qargs = (ptr(x0), ptr(noise), ptr(self.schedule.sqrt_acp), ptr(self.schedule.sqrt_1macp), ptr(timesteps), ptr(condition), cc,
+                 ptr(x_t), ptr(target) if vpred else None, n, c, v, self.schedule.num_train_timesteps)
+        if mask is None or not cc:
+            call("mi_qsample", *qargs)
+        else:
+            call("mi_qsample_drop", *qargs, ptr(mask))  # zero condition channels for dropped samples
         ctx = E.Ctx(self.arena, m._plans, grad_enabled=grad_enabled, prepacked=m.pack_all())
         ctx_tokens = None
         if context is not None:
-            ctx_tokens = ops.cast_bf16(context.contiguous().reshape(-1, context.shape[2]))
+            context = context.contiguous()
+            if mask is None:
+                ctx_tokens = ops.cast_bf16(context.reshape(-1, context.shape[2]))
+            else:  # zero context rows for dropped samples
+                ctx_tokens = torch.empty((n * context.shape[1], context.shape[2]), dtype=torch.bfloat16, device=context.device)
+                call("mi_cast_bf16_drop", ptr(context), ptr(ctx_tokens), ptr(mask), n, context.shape[1] * context.shape[2])
+        if mask is not None and class_labels is not None:  # the effective labels: the embedding and its backward both read these
+            labels = torch.empty_like(class_labels)
+            call("mi_select_labels", ptr(class_labels), ptr(mask), self.null_class, ptr(labels), n)
+            class_labels = labels
         pred = m._run(ctx, x_t, timesteps, need_dx=False, class_labels=class_labels, context=ctx_tokens)
         if pred.shape[-1] != target.shape[1]:  # k_mse indexes both with ONE channel count
             raise ValueError(f"prediction has {pred.shape[-1]} channels, the target {target.shape[1]}")
-        return ctx, pred, target, (n, v), (x_t, target, ctx_tokens, condition)
+        return ctx, pred, target, (n, v), (x_t, target, ctx_tokens, condition, class_labels, mask)
 
-    def _forward(self, x0, noise, timesteps, class_labels=None, context=None, condition=None):
+    def _forward(self, x0, noise, timesteps, class_labels=None, context=None, condition=None, drop=None):
         """q-sample -> UNet -> MSE (+ its gradient).  x0/noise: fp32 NCDHW, timesteps: int64 [N]; class_labels: int64 [N], only for
         a net built with num_class_embeds; context: fp32 [N, tokens, cross_attention_dim], only for with_conditioning=True;
-        condition: fp32 NC'[D]HW concatenated un-noised behind the noised channels (mode="concat")."""
-        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition)
+        condition: fp32 NC'[D]HW concatenated un-noised behind the noised channels (mode="concat"); drop: bool / uint8 [N], the
+        samples that train without their conditioning (class docstring)."""
+        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition, drop)
         self.arena.grad.zero_()
-        ctx, pred, target, (n, v), keep = self._predict(True, x0, noise, timesteps, class_labels, context, condition, cc)
+        ctx, pred, target, (n, v), keep = self._predict(True, x0, noise, timesteps, class_labels, context, condition, cc, drop)
         dpred = torch.empty_like(pred)
         call("mi_mse_fwd_bwd", ptr(pred), ptr(target), ptr(dpred), ptr(self.loss), n, pred.shape[-1], v, 1.0)
         self._keep = keep  # read by kernels still in flight / by the second graph of a split capture
         return ctx.tape, pred, dpred
 
-    def _eval_forward(self, meter, x0, noise, timesteps, class_labels=None, context=None, condition=None):
+    def _eval_forward(self, meter, x0, noise, timesteps, class_labels=None, context=None, condition=None, drop=None):
         """LDM.validate_epoch's batch (T-LDM:206-229): q-sample -> UNet -> mse_loss against the noise / velocity; _forward's inputs and
         checks, no tape, no gradient tensor."""
-        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition)
-        _, pred, target, (n, v), _ = self._predict(False, x0, noise, timesteps, class_labels, context, condition, cc)
+        cc = self._check_inputs(x0, noise, timesteps, class_labels, context, condition, drop)
+        _, pred, target, (n, v), _ = self._predict(False, x0, noise, timesteps, class_labels, context, condition, cc, drop)
         call("mi_mse_eval", ptr(pred), ptr(target), ptr(meter.acc), n, pred.shape[-1], v)
 
 
@@ -599,7 +653,7 @@ class LDMTrainer(DDPMTrainer):
         latents = autoencoder.encode_stage_2_inputs(images)   (no grad: T-LDM:154-156)  ->  * scale_factor  ->  q-sample -> UNet
         -> MSE -> backward -> clip -> AdamW
 
-    step(images, eps, noise, timesteps[, class_labels][, context=][, condition=]): images fp32 NC[D]HW; eps fp32, latent-shaped -- the torch.randn_like of
+    step(images, eps, noise, timesteps[, class_labels][, context=][, condition=][, drop=]): images fp32 NC[D]HW; eps fp32, latent-shaped -- the torch.randn_like of
     AutoencoderKL.sampling (AEKL:786-787) made an input so that a captured graph sees fresh noise and tests can pin it; noise fp32,
     latent-shaped (T-LDM:159); timesteps int64 [N].  The encoder runs tape-less on the same HIP kernels inside the same hipGraph.
     `scale_factor`: 1 / std of the first batch's latents (T-LDM:110-112) -- `estimate_scale_factor` -- or given."""
@@ -634,14 +688,16 @@ class LDMTrainer(DDPMTrainer):
         call("mi_scale_f32", ptr(z), self.scale_factor, z.numel())
         return z
 
-    def _forward(self, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
+    def _forward(self, images, eps, noise, timesteps, class_labels=None, context=None, condition=None, drop=None):
         """condition: latent-shaped fp32 tensor (e.g. the label mask resampled to the latent grid) concatenated un-noised behind the
-        scaled latents -- BASELINE configs[4]."""
-        return super()._forward(self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition)
+        scaled latents -- BASELINE configs[4]; drop: DDPMTrainer's condition-dropout mask (refused before the encoder runs)."""
+        self._check_drop(drop, images, class_labels, context, condition)
+        return super()._forward(self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition, drop)
 
-    def _eval_forward(self, meter, images, eps, noise, timesteps, class_labels=None, context=None, condition=None):
+    def _eval_forward(self, meter, images, eps, noise, timesteps, class_labels=None, context=None, condition=None, drop=None):
         """T-LDM:206-229: latents = autoencoder.encode_stage_2_inputs(images) * scale_factor, then the diffusion batch above."""
-        return super()._eval_forward(meter, self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition)
+        self._check_drop(drop, images, class_labels, context, condition)
+        return super()._eval_forward(meter, self._scaled_latents(images, eps), noise, timesteps, class_labels, context, condition, drop)
 
 
 class AETrainer(_ArenaTrainer):
