@@ -425,6 +425,23 @@ int mi_ddpm_step_guided(float* x, const void* model_out, const float* noise, con
                         void* x_cl, int x_cl_cs, int N, int C, int64_t V, int clip, hipStream_t stream);
 int mi_ddim_step_guided(float* x, const void* model_out, const float* noise, const float* rows, const int64_t* row_index,
                         const float* guidance, void* x_cl, int x_cl_cs, int N, int C, int64_t V, int flags, hipStream_t stream);
+/* one step of image-conditioned sampling: masked inpainting in the manner of RePaint (Lugmayr et al. 2022; not part of the reference:
+ * PARITY UNPINNED), composited inside the update launch.  The arguments of mi_ddim_step_guided -- guidance may be NULL: unguided,
+ * model_out of batch N, x_cl of batch N -- with ddim selecting the scheduler (0: table = the [T][5] coefficients of mi_ddpm_step and
+ * index = t; else the DDIM rows and the row index), and
+ *   mask: fp32 [N][V], one value per voxel for every channel;  image, known_noise: fp32 NCDHW, the known content and its noise;
+ *   known: [rows][4] fp32, indexed by the same device scalar as table = sqrt(A_next), sqrt(1 - A_next), sqrt(A_t / A_next),
+ *   sqrt(1 - A_t / A_next), A_next the level the step arrives at (the last two are the host's, for mi_renoise).
+ * Per element, m = mask[n][v]:   m >= 1: the value of the entries above (image and known_noise are not read);
+ *   m <= 0: known[0] image + known[1] known_noise (model_out, x and noise are not read);   else m x_gen + (1 - m) x_known.
+ * Mask-1 voxels carry the bits of the entries above; a NaN in a buffer that is not read does not reach x or x_cl */
+int mi_step_inpaint(float* x, const void* model_out, const float* noise, const float* table, const int64_t* index, const float* guidance,
+                    const float* mask, const float* image, const float* known_noise, const float* known, void* x_cl, int x_cl_cs, int N,
+                    int C, int64_t V, int flags, int ddim, hipStream_t stream);
+/* one forward-diffusion move (resampling between two steps of the entry above): x = a x + b noise in place, fp32 NCDHW; the bf16 copy
+ * goes into the first C channels of `halves` (1, or 2 for a guided loop) batches of x_cl (optional, NDHWC, voxel pitch x_cl_cs >= C) */
+int mi_renoise(float* x, const float* noise, float a, float b, void* x_cl, int x_cl_cs, int N, int halves, int C, int64_t V,
+               hipStream_t stream);
 /* loss = mean((pred - target)^2); dpred = grad_scale * 2 (pred - target) / numel (grad_scale 1.0 = F.mse_loss(...).backward());
  * pred NDHWC bf16 and target NCDHW fp32 must BOTH have C channels (the caller checks: a 9-channel target read with C = 8 lines up
  * for the first image only) */

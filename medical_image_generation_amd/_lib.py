@@ -115,6 +115,8 @@ _SIGS = {
     "mi_ddim_step": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
     "mi_ddpm_step_guided": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
     "mi_ddim_step_guided": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
+    "mi_step_inpaint": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, _p],
+    "mi_renoise": [_p, _p, _f, _f, _p, _i, _i, _i, _i, _l, _p],
     "mi_qsample_drop": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p, _p],
     "mi_select_labels": [_p, _p, _l, _p, _i, _p],
     "mi_cast_bf16_drop": [_p, _p, _p, _i, _l, _p],
@@ -143,7 +145,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 
 def exported_symbols() -> list[str]:

@@ -339,6 +339,74 @@ __global__ void k_step_guided(float* __restrict__ x, const bf16* __restrict__ mo
     }
   }
 }
+// One step of image-conditioned sampling (masked inpainting in the manner of RePaint, Lugmayr et al. 2022; not part of the reference: PARITY
+// UNPINNED) on either scheduler, unguided or guided: the step of the kernels above where mask[n][v] >= 1, the known content at the level
+// the step arrives at where mask <= 0, their mix in between -- compositing inside the update launch, so a step stays ONE forward plus
+// ONE launch.  known: [rows][4] beside the step table, indexed by the same device scalar; q0 = sqrt(A_next), q1 = sqrt(1 - A_next).
+//   m >= 1:  x_next = ddpm_update / ddim_update(...)            (image and known_noise are not read)
+//   m <= 0:  x_next = q0 image + q1 known_noise                 (the model output, x and z are not read)
+//   else:    x_next = m x_gen + (1 - m) x_known
+// A selection, not a lerp evaluated everywhere: a NaN in a buffer the rule does not read (the model's bf16 overflow inside a region
+// that is overwritten anyway) does not reach the output, and mask-1 voxels carry the bits of the kernels above.  mask fp32 [N][V]
+// (one value per voxel, every channel), image / known_noise fp32 NCDHW; x, mo_cl, z, x_cl as k_step_guided (GUIDED) or k_ddim_step.
+template <bool DDIM, bool GUIDED>
+__global__ void k_step_inpaint(float* __restrict__ x, const bf16* __restrict__ mo_cl, const float* __restrict__ z, const float* __restrict__ table,
+                               const int64_t* __restrict__ index, const float* __restrict__ guidance, const float* __restrict__ mask,
+                               const float* __restrict__ image, const float* __restrict__ known_noise, const float* __restrict__ known,
+                               bf16* __restrict__ x_cl, int x_cl_cs, int C, int64_t V, int64_t total, int flags) {
+  const float* k = table + index[0] * 5;
+  const float k0 = k[0], k1 = k[1], k2 = k[2], k3 = k[3], k4 = k[4];
+  const float* q = known + index[0] * 4;
+  const float q0 = q[0], q1 = q[1];
+  const float w = GUIDED ? guidance[0] : 0.f;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t n = i / V, v = i - n * V;
+    const int64_t iu = i + total;  // the same voxel of the unconditional half (GUIDED)
+    const float m = mask[i];
+    for (int c = 0; c < C; ++c) {
+      const int64_t s = (n * C + c) * V + v;
+      float xg = 0.f, xk = 0.f;
+      if (!(m <= 0.f)) {  // regenerated, at least in part
+        float mo = bf2f(mo_cl[i * C + c]);
+        if (GUIDED) {
+          const float mu = bf2f(mo_cl[iu * C + c]);
+          mo = mu + w * (mo - mu);
+        }
+        xg = DDIM ? ddim_update(x[s], mo, z, s, k0, k1, k2, k3, k4, flags) : ddpm_update(x[s], mo, z, s, k0, k1, k2, k3, k4, flags);
+      }
+      if (!(m >= 1.f)) {  // known, at least in part
+        xk = q0 * image[s];
+        if (q1 != 0.f) xk += q1 * known_noise[s];
+      }
+      const float xn = m >= 1.f ? xg : (m <= 0.f ? xk : m * xg + (1.f - m) * xk);
+      x[s] = xn;
+      if (x_cl) {
+        const bf16 b = f2bf(xn);
+        x_cl[i * x_cl_cs + c] = b;
+        if (GUIDED) x_cl[iu * x_cl_cs + c] = b;
+      }
+    }
+  }
+}
+// One forward-diffusion move between two replays of the step above (resampling): x = a x + b z in place, a = sqrt(A_t / A_next) and
+// b = sqrt(1 - A_t / A_next) of the step being undone, by value.  No model and no mask: a known region renoised this way is a valid
+// sample of the higher level.  The bf16 copy goes into the sample channels of `halves` (1, or 2 when guided) batches of x_cl.
+__global__ void k_renoise(float* __restrict__ x, const float* __restrict__ z, float a, float b, bf16* __restrict__ x_cl, int x_cl_cs, int halves,
+                          int C, int64_t V, int64_t total) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    int64_t n = i / V, v = i - n * V;
+    for (int c = 0; c < C; ++c) {
+      const int64_t s = (n * C + c) * V + v;
+      const float xn = a * x[s] + b * z[s];
+      x[s] = xn;
+      if (x_cl) {
+        const bf16 h = f2bf(xn);
+        x_cl[i * x_cl_cs + c] = h;
+        if (halves == 2) x_cl[(i + total) * x_cl_cs + c] = h;
+      }
+    }
+  }
+}
 // loss = mean((pred - target)^2) over all elements; dpred = 2 (pred - target) / numel * loss_scale.
 // pred NDHWC bf16, target NCDHW fp32, dpred NDHWC bf16.  loss accumulated with one atomic per block into *loss_sum.
 __global__ void k_mse(const bf16* __restrict__ pred, const float* __restrict__ target, bf16* __restrict__ dpred,
@@ -716,6 +784,27 @@ int mi_ddim_step_guided(float* x, const void* model_out, const float* noise, con
   if (N <= 0 || V <= 0 || C <= 0 || !x || !model_out || !noise || !rows || !row_index || !guidance || (x_cl && x_cl_cs < C)) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_step_guided<true>, dim3(grid_for(total)), dim3(kThreads), 0, st, x, (const bf16*)model_out, noise, rows, row_index,
                      guidance, (bf16*)x_cl, x_cl_cs, C, V, total, flags);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+int mi_step_inpaint(float* x, const void* model_out, const float* noise, const float* table, const int64_t* index, const float* guidance,
+                    const float* mask, const float* image, const float* known_noise, const float* known, void* x_cl, int x_cl_cs, int N, int C,
+                    int64_t V, int flags, int ddim, hipStream_t st) {
+  int64_t total = (int64_t)N * V;
+  if (N <= 0 || V <= 0 || C <= 0 || !x || !model_out || !noise || !table || !index || !mask || !image || !known_noise || !known ||
+      (x_cl && x_cl_cs < C))
+    return MI_ERR_BAD_ARG;
+  auto kern = ddim ? (guidance ? k_step_inpaint<true, true> : k_step_inpaint<true, false>)
+                   : (guidance ? k_step_inpaint<false, true> : k_step_inpaint<false, false>);
+  hipLaunchKernelGGL(kern, dim3(grid_for(total)), dim3(kThreads), 0, st, x, (const bf16*)model_out, noise, table, index, guidance, mask, image,
+                     known_noise, known, (bf16*)x_cl, x_cl_cs, C, V, total, flags);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+int mi_renoise(float* x, const float* noise, float a, float b, void* x_cl, int x_cl_cs, int N, int halves, int C, int64_t V, hipStream_t st) {
+  int64_t total = (int64_t)N * V;
+  if (N <= 0 || V <= 0 || C <= 0 || !x || !noise || (halves != 1 && halves != 2) || (x_cl && x_cl_cs < C)) return MI_ERR_BAD_ARG;
+  hipLaunchKernelGGL(k_renoise, dim3(grid_for(total)), dim3(kThreads), 0, st, x, noise, a, b, (bf16*)x_cl, x_cl_cs, halves, C, V, total);
   MI_CHECK_LAUNCH();
   return 0;
 }

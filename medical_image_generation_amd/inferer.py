@@ -20,6 +20,14 @@ reference; PARITY UNPINNED): every step is ONE forward at batch 2N -- the condit
 `mi_ddpm_step_guided` / `mi_ddim_step_guided` launch that forms m = m_uncond + w (m_cond - m_uncond) and continues with the unguided
 arithmetic.  Null means zeros for the cross-attention context and the concatenated condition channels, and `null_class` for the
 class route -- what trainer.DDPMTrainer(..., null_class=).step(..., drop) trains.  w is a device scalar: one graph serves every scale.
+
+Image-conditioned sampling (`img2img`, `inpaint`; SDEdit, Meng et al. 2022, and masked inpainting in the manner of RePaint, Lugmayr et al.
+2022 -- not part of the reference; PARITY UNPINNED): a run may start part-way down the step list, from the image noised to that level,
+and with a mask every step is still ONE forward plus ONE launch -- `mi_step_inpaint` composites inside the update: the generated value
+where the mask is 1, the known image at the level the step arrives at where it is 0 (a per-step `known` table beside the step table).
+Resampling is a list of moves: denoising steps, replayed from the same graph, and forward-diffusion moves (`mi_renoise`) between them.
+Mask, image and known-region noise are buffers, the known rows a table the captured step already points at; the start and the move list
+only choose which replays happen: one captured graph serves every run-time choice.
 """
 from __future__ import annotations
 
@@ -41,6 +49,37 @@ def betas(schedule, num_train_timesteps, beta_start, beta_end):
     raise ValueError(f"unknown schedule {schedule}")
 
 
+def _known_rows(a, a_next):
+    """fp32 [len(a), 4] = sqrt(A_next), sqrt(1 - A_next), sqrt(A_t / A_next), sqrt(1 - A_t / A_next) for steps that leave the level a
+    (fp64) and arrive at a_next: the known region at the arrival level is [0] image + [1] noise (`mi_step_inpaint`), and [2] x + [3] noise
+    takes a sample back from a_next to a (`mi_renoise`).  fp64 with every radicand clamped at 0, kept as fp32."""
+    q = a / a_next
+    return torch.stack([a_next.clamp(min=0).sqrt(), (1 - a_next).clamp(min=0).sqrt(), q.clamp(min=0).sqrt(), (1 - q).clamp(min=0).sqrt()],
+                       dim=1).float().contiguous()
+
+
+def resample_moves(n_steps, jump_length, jump_n_sample, start=0):
+    """The move list of a resampled ("time travel") run over steps start .. n_steps - 1: [("d", i) | ("n", i), ...] -- ("d", i) is
+    denoising step i, ("n", i) undoes step i with one forward-diffusion move (`mi_renoise`).  The d moves run in order; each time the
+    number of completed steps p (counted from `start`) reaches a multiple of jump_length with steps left, jump_n_sample - 1 times:
+    n for the last jump_length steps, newest first, then d for the same steps again.  Jumps never go above `start`.
+        resample_moves(4, 2, 2) = d0 d1 n1 n0 d0 d1 d2 d3;   forwards: n + (r - 1) j floor((n - 1) / j) for n = n_steps - start
+    In the manner of RePaint (Lugmayr et al. 2022), but the order is this project's own: PARITY UNPINNED."""
+    n, j, r = int(n_steps) - int(start), int(jump_length), int(jump_n_sample)
+    if start < 0 or n < 1:
+        raise ValueError(f"resample: start {start} leaves no step of {n_steps}")
+    if j < 1 or r < 1 or j > n:
+        raise ValueError(f"resample: jump_length must lie in [1, {n}] and jump_n_sample be at least 1, got ({jump_length}, {jump_n_sample})")
+    moves = []
+    for i in range(start, n_steps):
+        moves.append(("d", i))
+        if (i + 1 - start) % j == 0 and i + 1 < n_steps:
+            for _ in range(r - 1):
+                moves += [("n", k) for k in range(i, i - j, -1)]
+                moves += [("d", k) for k in range(i - j + 1, i + 1)]
+    return moves
+
+
 class DDPMScheduler:
     """`generative.networks.schedulers.DDPMScheduler` as train_ldm.py:74 constructs it (variance_type "fixed_small")."""
 
@@ -60,7 +99,7 @@ class DDPMScheduler:
         sigma[0] = 0.0  # no noise is added at t = 0
         self._coef = torch.stack([1 / acp.sqrt(), (1 - acp).sqrt(), prev.sqrt() * b / (1 - acp), (1 - b).sqrt() * (1 - prev) / (1 - acp), sigma],
                                  dim=1).float().contiguous()
-        self._coef_dev = None
+        self._coef_dev = self._known_dev = None
         self.set_timesteps(num_train_timesteps)
 
     def set_timesteps(self, num_inference_steps, device=None):
@@ -77,6 +116,18 @@ class DDPMScheduler:
         if self._coef_dev is None or self._coef_dev.device != torch.device(device):
             self._coef_dev = self._coef.to(device)
         return self._coef_dev
+
+    def known_rows(self):
+        """fp32 [T, 4], row t: the known-region constants (`_known_rows`) of the step that leaves t -- it arrives at alphas_cumprod[t - 1]
+        (1 at t = 0), the level this scheduler's coefficients assume whatever the stride."""
+        acp = self.alphas_cumprod.double()
+        return _known_rows(acp, torch.cat([torch.ones(1, dtype=torch.float64), acp[:-1]]))
+
+    def known_coefficients(self, device):
+        """The device table `mi_step_inpaint` reads beside coefficients(): [num_train_timesteps, 4], one allocation per device."""
+        if self._known_dev is None or self._known_dev.device != torch.device(device):
+            self._known_dev = self.known_rows().to(device)
+        return self._known_dev
 
     def add_noise(self, original_samples, noise, timesteps):
         a = self.alphas_cumprod.to(original_samples.device)[timesteps]
@@ -125,7 +176,7 @@ class DDIMScheduler:
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]  # the level "before" t = 0
         self.first_alpha_cumprod = torch.tensor(0.0)  # the level "after" t = T - 1 (inversion): pure noise
-        self._table = None
+        self._table = self._known = None
         # every training timestep, descending; steps_offset shifts the strided subsets of set_timesteps only
         self.num_inference_steps = num_train_timesteps
         self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1, dtype=torch.int64)
@@ -169,6 +220,21 @@ class DDIMScheduler:
             self._table = torch.zeros(self.num_train_timesteps, 5, dtype=F32, device=device)
         return self._table
 
+    def known_rows(self, eta=0.0):
+        """fp32 [n_steps, 4] in loop order: the known-region constants (`_known_rows`) of the denoising steps, each arriving at the `ap` of
+        its row (final_alpha_cumprod on the last).  eta does not enter: the marginal at the next level is ap whatever sigma is."""
+        acp, ratio = self.alphas_cumprod.double(), self.num_train_timesteps // self.num_inference_steps
+        t = self.timesteps.cpu()
+        p = t - ratio
+        return _known_rows(acp[t], torch.where(p >= 0, acp[p.clamp(min=0)], self.final_alpha_cumprod.double()))
+
+    def known_coefficients(self, device):
+        """The device table `mi_step_inpaint` reads beside coefficients(): [num_train_timesteps, 4], one allocation per device at full
+        capacity, refilled by the loop before it steps -- a captured graph survives set_timesteps."""
+        if self._known is None or self._known.device != torch.device(device):
+            self._known = torch.zeros(self.num_train_timesteps, 4, dtype=F32, device=device)
+        return self._known
+
     def add_noise(self, original_samples, noise, timesteps):
         a = self.alphas_cumprod.to(original_samples.device)[timesteps]
         shape = (-1,) + (1,) * (original_samples.ndim - 1)
@@ -206,10 +272,11 @@ class DDIMScheduler:
 class _Loop:
     """One captured denoising step, replayed over scheduler.timesteps."""
 
-    def __init__(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False):
+    def __init__(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False, inpaint=False):
         """cond_channels: channels of a mode="concat" conditioning tensor that sit, un-noised, behind the sample's channels in the model
         input; context_shape: (tokens, cross_attention_dim) of a mode="crossattn" conditioning; labels: the model reads class labels;
-        guided: classifier-free guidance -- the model runs at batch 2N (condition, then null condition), the sample stays at batch N."""
+        guided: classifier-free guidance -- the model runs at batch 2N (condition, then null condition), the sample stays at batch N;
+        inpaint: the update launch is `mi_step_inpaint` on this loop's image, mask [N, V], known-region noise and known table."""
         self.m, self.sch = model, scheduler
         n, c = shape[0], shape[1]
         self.guided = bool(guided)
@@ -231,6 +298,12 @@ class _Loop:
         self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its table with: t (DDPM), step i (DDIM)
         self.tn = torch.zeros(nb, dtype=torch.int64, device=device)  # the timestep the model reads
         self.coef = scheduler.coefficients(device)
+        self.inpaint = bool(inpaint)
+        if self.inpaint:
+            self.image = torch.zeros(shape, dtype=F32, device=device)       # the known content, at the sample's level of abstraction
+            self.mask = torch.ones((n, self.v), dtype=F32, device=device)   # 1: regenerate, 0: keep, between: blend
+            self.zk = torch.zeros(shape, dtype=F32, device=device)          # the noise of the known region
+            self.known = scheduler.known_coefficients(device)
         self.arena = model.arena(device)
         self.graph = None
         self.keys = ()  # conv plans whose weights are packed: once per run(), not per step (the weights do not change while sampling)
@@ -240,7 +313,10 @@ class _Loop:
         ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
         eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, class_labels=self.labels, context=self.ctx)
         flags = int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0)
-        if self.guided:  # eps holds both branches: the kernel combines them, steps, and rewrites the sample channels of both halves
+        if self.inpaint:  # the same step, composited with the known image inside the launch (guidance NULL: unguided)
+            call("mi_step_inpaint", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.w), ptr(self.mask), ptr(self.image),
+                 ptr(self.zk), ptr(self.known), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, flags, int(self.ddim))
+        elif self.guided:  # eps holds both branches: the kernel combines them, steps, and rewrites the sample channels of both halves
             call("mi_ddim_step_guided" if self.ddim else "mi_ddpm_step_guided", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t),
                  ptr(self.w), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, flags)
         else:
@@ -255,12 +331,19 @@ class _Loop:
             self.x_cl[h * self.n:(h + 1) * self.n, ..., :self.c].copy_(x_cl)
 
     def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None, eta=0.0, reverse=False,
-            class_labels=None, guidance_scale=None, null_class=None):
+            class_labels=None, guidance_scale=None, null_class=None, start=0, moves=None, image=None, mask=None, fresh=False,
+            known_noises=None):
         """eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps.
-        class_labels (int64 [N]), guidance_scale, null_class: what the loop was built for (labels / guided); filled before any step."""
+        class_labels (int64 [N]), guidance_scale, null_class: what the loop was built for (labels / guided); filled before any step.
+        start: index into the step list of the first step taken (input_noise is then a sample of that step's level); moves: the list
+        `resample_moves` returns, default one "d" per step from `start` -- `noises` holds one z per move, in move order.
+        image, mask ([N, V] fp32): an inpaint loop's known content; fresh: its noise zk is redrawn before every "d" move, else drawn
+        once; known_noises pins it: one tensor, or one per "d" move.  Draw order per "d" move: z, then zk."""
         if self.m._arena is not self.arena:  # the module moved (.to / .cuda): plans and graph point at the old buffers -> start over
             self.arena, self.graph, self.keys, self._pinned = self.m.arena(self.x.device), None, (), None
         n = self.n
+        if reverse and (self.inpaint or start or moves is not None):
+            raise ValueError("the inversion rows take no mask, start or move list")
         if self.cc:  # mode="concat": model_input = cat([image, conditioning], dim=1) at every step; written once, the steps rewrite `image`
             self.x_cl[:n, ..., self.c:].copy_(ops.to_channels_last(conditioning))
         elif self.ctx is not None:  # mode="crossattn": the context token matrix is a constant of the loop
@@ -282,6 +365,21 @@ class _Loop:
                 steps.reverse()
             self.coef[:len(steps)].copy_(self.sch.rows(eta, reverse))
             self.t.zero_()
+        if moves is None:
+            moves = [("d", i) for i in range(start, len(steps))]
+        known = None  # the host's copy of the known rows: mi_renoise takes its two factors by value
+        if self.inpaint or any(kind == "n" for kind, _ in moves):
+            known = self.sch.known_rows(eta) if self.ddim else self.sch.known_rows()
+        if self.inpaint:
+            if self.ddim:
+                self.known[:len(steps)].copy_(known)
+            self.image.copy_(image)
+            self.mask.copy_(mask)
+            single = torch.is_tensor(known_noises)
+            if single:
+                self.zk.copy_(known_noises)
+            elif known_noises is None and not fresh:
+                self.zk.normal_(generator=generator)
         keep = self.x.clone()
         if not self.m._plans or len(self.keys) != len(self.m._plans):
             self.keys = ()
@@ -301,15 +399,32 @@ class _Loop:
                 self._step()
             self._pinned = (dict(self.m._plans), dict(ops._ws_cache), self.arena)  # keep what the graph points at alive
         self._load(keep)
-        for i, t in enumerate(steps):
+        done = 0  # "d" moves so far
+        for j, (kind, i) in enumerate(moves):
+            t = steps[i]
+            if kind == "n":  # undo step i: one forward-diffusion move from the level it arrived at, eager, between two replays
+                if noises is not None:
+                    self.z.copy_(noises[j])
+                else:
+                    self.z.normal_(generator=generator)
+                row = known[i if self.ddim else t]
+                call("mi_renoise", ptr(self.x), ptr(self.z), float(row[2]), float(row[3]), ptr(self.x_cl), self.c + self.cc, self.n,
+                     2 if self.guided else 1, self.c, self.v)
+                continue
             self.t.fill_(i if self.ddim else t)
             self.tn.fill_(t)
             if self.ddim and (reverse or eta == 0):
                 pass  # deterministic rows (sigma = 0): the kernel does not read z
             elif noises is not None:
-                self.z.copy_(noises[i])
+                self.z.copy_(noises[j])
             elif self.ddim or t > 0:
                 self.z.normal_(generator=generator)
+            if self.inpaint and not single:
+                if known_noises is not None:
+                    self.zk.copy_(known_noises[done])
+                elif fresh:
+                    self.zk.normal_(generator=generator)
+            done += 1
             if self.graph is not None:
                 self.graph.replay()
             else:
@@ -326,10 +441,10 @@ class DiffusionInferer:
         self.scheduler = scheduler
         self._loops = {}
 
-    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False):
-        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape, bool(guided), bool(labels))
+    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False, inpaint=False):
+        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape, bool(guided), bool(labels), bool(inpaint))
         if key not in self._loops:
-            self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape, guided, labels)
+            self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape, guided, labels, inpaint)
         return self._loops[key]
 
     @staticmethod
@@ -415,12 +530,92 @@ class DiffusionInferer:
                          eta=eta, class_labels=class_labels, guidance_scale=guidance_scale, null_class=null_class)
         return (image, inter) if save_intermediates else image
 
+    @staticmethod
+    def _start(scheduler, strength):
+        """strength in (0, 1] -> the index into scheduler.timesteps of the first step taken: the last min(int(n strength), n) steps run."""
+        n = len(scheduler.timesteps)
+        n_run = min(int(n * strength), n) if 0 < strength <= 1 else 0
+        if n_run == 0:
+            raise ValueError(f"strength must lie in (0, 1] and leave at least one of the {n} steps, got {strength}")
+        return n - n_run
+
+    @staticmethod
+    def _first_sample(image, input_noise, scheduler, start, generator):
+        """The sample a run enters step `start` with: input_noise itself at start 0, else the image noised to that step's level."""
+        if input_noise is None:
+            input_noise = torch.randn(image.shape, generator=generator, device=image.device, dtype=F32)
+        if tuple(input_noise.shape) != tuple(image.shape):
+            raise ValueError("input_noise must have the image's shape")
+        if start == 0:
+            return input_noise.float()
+        return scheduler.add_noise(image.float(), input_noise.float(), int(scheduler.timesteps[start]))
+
+    @staticmethod
+    def _check_mask(mask, shape):
+        if not torch.is_tensor(mask) or not (mask.dtype == torch.bool or mask.is_floating_point()):
+            raise ValueError("mask must be a bool or float tensor (1: regenerate, 0: keep)")
+        if mask.dim() != len(shape) or mask.shape[1] != 1 or mask.shape[0] not in (1, shape[0]) or tuple(mask.shape[2:]) != tuple(shape[2:]):
+            raise ValueError(f"mask must be [N, 1, *spatial] or [1, 1, *spatial] for an image of shape {tuple(shape)}, got {tuple(mask.shape)}")
+
+    @torch.no_grad()
+    def img2img(self, image, diffusion_model, strength, input_noise=None, scheduler=None, conditioning=None, mode="crossattn", verbose=True,
+                noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None, guidance_scale=None, null_class=None):
+        """Partial-noise start (SDEdit's `strength`; the noise-and-reconstruct recipe of anomaly maps; not part of the reference: PARITY
+        UNPINNED): the last n_run = min(int(n strength), n) of the scheduler's n steps, from scheduler.add_noise(image, input_noise,
+        timesteps[n - n_run]) -- or from input_noise itself when all n run: strength 1 is `sample(input_noise)`.  The loop, kernels and
+        captured graph of `sample`; the other arguments as there (`noises`: one z per step taken)."""
+        scheduler = scheduler or self.scheduler
+        start = self._start(scheduler, strength)
+        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
+                                                                       null_class)
+        x = self._first_sample(image, input_noise, scheduler, start, generator)
+        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None, class_labels is not None)
+        return loop.run(x, noises=noises, generator=generator, use_graph=use_graph, conditioning=conditioning, eta=eta, class_labels=class_labels,
+                        guidance_scale=guidance_scale, null_class=null_class, start=start)
+
+    @torch.no_grad()
+    def inpaint(self, image, mask, diffusion_model, strength=1.0, input_noise=None, known_noise=None, known_noises=None, resample=None,
+                scheduler=None, conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0,
+                class_labels=None, guidance_scale=None, null_class=None, on_step=None):
+        """Regenerate the region where mask is 1 so that it agrees with the image kept where mask is 0 (in the manner of RePaint, Lugmayr
+        et al. 2022; not part of the reference: PARITY UNPINNED).  mask: bool or float [N, 1, *spatial] or [1, 1, *spatial]; values
+        between 0 and 1 blend (a feathered edge).  After every step the kept region is the image at the level the step arrived at,
+        sqrt(A_next) image + sqrt(1 - A_next) zk, written by the step's own update launch; with set_alpha_to_one (or DDPM's t = 0) the
+        last level is the image itself, so kept voxels come back exactly.
+        strength, input_noise: as `img2img` (strength 1 starts from input_noise).
+        known_noise: "fixed" -- zk is drawn once per run (deterministic with DDIM eta = 0) -- or "fresh" -- redrawn before every
+        denoising move, as RePaint does; None: "fresh" when the sampler draws per-step noise (DDPM, DDIM with eta > 0), else "fixed".
+        known_noises pins zk: one tensor, or one per denoising move.
+        resample=(jump_length, jump_n_sample): `resample_moves` -- without it the region does not harmonise with its surroundings when
+        the model was not trained for inpainting.  noises: one z per move of either kind, in move order.
+        on_step(i, t, x): called after every denoising move.  The other arguments as `sample`."""
+        scheduler = scheduler or self.scheduler
+        self._check_mask(mask, image.shape)
+        start = self._start(scheduler, strength)
+        if known_noise not in (None, "fixed", "fresh"):
+            raise ValueError(f"known_noise must be 'fixed', 'fresh' or None, got {known_noise!r}")
+        n_steps = len(scheduler.timesteps)
+        moves = None if resample is None else resample_moves(n_steps, resample[0], resample[1], start)
+        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
+                                                                       null_class)
+        ddim = isinstance(scheduler, DDIMScheduler)
+        fresh = (not ddim or eta > 0) if known_noise is None else known_noise == "fresh"
+        x = self._first_sample(image, input_noise, scheduler, start, generator)
+        m = mask.to(device=image.device, dtype=F32).expand((image.shape[0],) + tuple(mask.shape[1:])).reshape(image.shape[0], -1).contiguous()
+        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None,
+                          class_labels is not None, inpaint=True)
+        return loop.run(x, noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning, eta=eta,
+                        class_labels=class_labels, guidance_scale=guidance_scale, null_class=null_class, start=start, moves=moves,
+                        image=image.float(), mask=m, fresh=fresh, known_noises=known_noises)
+
     @torch.no_grad()
     def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True, class_labels=None,
-               guidance_scale=None, null_class=None):
+               guidance_scale=None, null_class=None, mask=None):
         """Image-to-noise DDIM inversion: DDIMScheduler.reversed_step over ascending timesteps in the fused loop of `sample` (same
         captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler.
-        class_labels, guidance_scale, null_class: as in `sample`."""
+        class_labels, guidance_scale, null_class: as in `sample`.  mask: refused -- there is no inversion of a masked region."""
+        if mask is not None:
+            raise ValueError("invert takes no mask: the inversion rows have no known region (use inpaint to regenerate one)")
         scheduler = scheduler or self.scheduler
         if not isinstance(scheduler, DDIMScheduler):
             raise TypeError(f"invert needs a DDIMScheduler (reversed_step), not {type(scheduler).__name__}")
@@ -461,7 +656,41 @@ class LatentDiffusionInferer(DiffusionInferer):
 
     @torch.no_grad()
     def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True,
-               class_labels=None, guidance_scale=None, null_class=None):
+               class_labels=None, guidance_scale=None, null_class=None, mask=None):
         """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor)."""
+        if mask is not None:
+            raise ValueError("invert takes no mask: the inversion rows have no known region (use inpaint to regenerate one)")
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
         return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class)
+
+    @torch.no_grad()
+    def img2img(self, image, autoencoder_model, diffusion_model, strength, input_noise=None, **kwargs):
+        """DiffusionInferer.img2img on encode_stage_2_inputs(image) * scale_factor (input_noise has the latent's shape), then decoded."""
+        latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
+        latent = super().img2img(latent, diffusion_model, strength, input_noise, **kwargs)
+        return autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
+
+    @staticmethod
+    def latent_mask(mask, latent_spatial):
+        """An image-space mask [N, 1, *spatial] on the latent grid: the mean over each latent voxel's footprint (a box of image extent /
+        latent extent per axis, which must be an integer) -- a soft mask, fp32, fractional where the footprint straddles the edge."""
+        sp = tuple(mask.shape[2:])
+        if len(sp) != len(latent_spatial) or any(l < 1 or s % l for s, l in zip(sp, latent_spatial)):
+            raise ValueError(f"mask extent {sp} is no integer multiple of the latent extent {tuple(latent_spatial)}")
+        f = tuple(s // l for s, l in zip(sp, latent_spatial))
+        pool = {1: torch.nn.functional.avg_pool1d, 2: torch.nn.functional.avg_pool2d, 3: torch.nn.functional.avg_pool3d}[len(sp)]
+        return pool(mask.float(), kernel_size=f, stride=f)
+
+    @torch.no_grad()
+    def inpaint(self, image, mask, autoencoder_model, diffusion_model, strength=1.0, input_noise=None, paste_back=True, **kwargs):
+        """DiffusionInferer.inpaint in the latent space: the image encoded (* scale_factor), the mask reduced by `latent_mask` (once per
+        call), the loop, then decoded.  paste_back: return mask * decoded + (1 - mask) * image in image space -- the autoencoder is
+        lossy, and known voxels must come back exactly.  input_noise and the pinned noises have the latent's shape."""
+        self._check_mask(mask, image.shape)
+        latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
+        out = super().inpaint(latent, self.latent_mask(mask, latent.shape[2:]), diffusion_model, strength, input_noise, **kwargs)
+        out = autoencoder_model.decode_stage_2_outputs(out / self.scale_factor)
+        if paste_back:
+            m = mask.to(device=out.device, dtype=out.dtype)
+            out = m * out + (1 - m) * image.to(out.dtype)
+        return out

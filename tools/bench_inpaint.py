@@ -1,0 +1,162 @@
+"""What masked inpainting costs next to plain sampling, at shapes a user runs: the C4 net at 1 x 1 x 128^3 and the latent U-Net of the
+LDM configs (C3b) at 4 x 8 x 32^3, DDIM with eta 0, graph replay.
+
+    loop     ms per denoising step of `sample` and of `inpaint` (half of the volume masked, fixed known noise): host clock around the
+             call, ending in a device synchronise, the two alternated `--repeats` times in one process after a warm-up call each
+    launch   the update launch alone, `mi_ddim_step` against `mi_step_inpaint` with a mask of all 1, all 0, a contiguous half and all
+             0.5 (every buffer read), on an eta-1 row (z is read): HIP events around `--launches` launches that walk over sets of
+             buffers -- so many that what the plain launch touches exceeds `--footprint-mib` (default 384, above the 256 MiB of
+             Infinity Cache: a launch reads from HBM, as it does behind a forward) --, alternated `--repeats` times; GB/s = the
+             bytes the launch needs, from the shapes and the mask, over its time
+
+One JSON line per measurement.
+    python tools/bench_inpaint.py [--steps 50] [--repeats 7] [--launches 96] [--footprint-mib 384] [--only c4|c3b] [--part both|loop|launch]
+(`--part loop` under `rocprofv3 --kernel-trace --stats` gives the update kernels' time inside the replayed step.)
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def iso(levels):
+    return [[1] * 3] + [[2] * 3] * (levels - 1)
+
+
+def _net(kw):
+    import torch
+    from medical_image_generation_amd.unet import DiffusionModelUNet
+    net = DiffusionModelUNet(**kw)
+    for p in net.parameters():  # zero_module'd tensors: a zero output is not a measurement of anything
+        if float(p.detach().abs().max()) == 0:
+            torch.nn.init.normal_(p, std=0.02)
+    return net.cuda().eval()
+
+
+def loops(name, kw, shape, a):
+    import torch
+    from medical_image_generation_amd.inferer import DDIMScheduler, DiffusionInferer
+    net = _net(kw)
+    sch = DDIMScheduler(1000, "scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)
+    sch.set_timesteps(a.steps)
+    inf = DiffusionInferer(sch)
+    x, image, zk = (torch.randn(shape, device="cuda") for _ in range(3))
+    mask = torch.zeros((shape[0], 1) + tuple(shape[2:]), device="cuda")
+    mask[:, :, :shape[2] // 2] = 1.0
+    runs = {"sample": lambda: inf.sample(x, net, sch, verbose=False),
+            "inpaint": lambda: inf.inpaint(image, mask, net, input_noise=x, known_noises=zk, verbose=False)}
+    times = {k: [] for k in runs}
+    for fn in runs.values():
+        fn()  # plan creation + capture
+    torch.cuda.synchronize()
+    assert all(l.graph is not None for l in inf._loops.values()) and len(inf._loops) == 2
+    for _ in range(a.repeats):
+        for k, fn in runs.items():
+            t0 = time.perf_counter()
+            out = fn()
+            torch.cuda.synchronize()
+            times[k].append((time.perf_counter() - t0) / a.steps * 1e3)
+            assert torch.isfinite(out).all()
+    med = {k: statistics.median(v) for k, v in times.items()}
+    print(json.dumps(dict(measure="loop", config=name, shape=list(shape), steps=a.steps, repeats=a.repeats, hipgraph=True,
+                          ms_per_step={k: round(v, 4) for k, v in med.items()},
+                          ms_per_step_min_max={k: [round(min(v), 4), round(max(v), 4)] for k, v in times.items()},
+                          inpaint_over_sample=round(med["inpaint"] / med["sample"], 4))), flush=True)
+    del inf, net
+    torch.cuda.empty_cache()
+
+
+def launches(name, shape, a):
+    import torch
+    from medical_image_generation_amd._lib import call, ptr
+    from medical_image_generation_amd.inferer import DDIMScheduler
+    n, c = shape[0], shape[1]
+    v = 1
+    for s in shape[2:]:
+        v *= s
+    sch = DDIMScheduler(1000, "scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)
+    sch.set_timesteps(50)
+    table, known = sch.rows(1.0).cuda(), sch.known_rows(1.0).cuda()
+    idx = torch.full((1,), 25, dtype=torch.int64, device="cuda")
+    assert float(table[25, 4]) > 0  # z is read
+    el = n * c * v
+    n_sets = a.footprint_mib * 2 ** 20 // (el * 12) + 1  # x, model output, z, x_cl: what mi_ddim_step touches
+    sets = []
+    for _ in range(n_sets):
+        sets.append(dict(x=torch.randn(n, c, v, device="cuda"), mo=torch.randn(n, v, c, device="cuda").bfloat16(), z=torch.randn(n, c, v, device="cuda"),
+                         x_cl=torch.zeros(n, v, c, dtype=torch.bfloat16, device="cuda"), image=torch.randn(n, c, v, device="cuda"),
+                         zk=torch.randn(n, c, v, device="cuda"), mask=torch.ones(n, v, device="cuda")))
+    gen, kept, m = 4 + 2 + 4 + 4 + 2, 4 + 4 + 4 + 2, 4.0 / c  # bytes per element: x, model output, z in, x, x_cl out | image, zk in, x, x_cl out | mask
+    variants = {"mi_ddim_step": (None, gen), "inpaint mask 1": (1.0, gen + m), "inpaint mask 0": (0.0, kept + m),
+                "inpaint half": ("half", (gen + kept) / 2 + m), "inpaint mask 0.5": (0.5, gen + 4 + 4 + m)}
+
+    def fill(value):
+        for s in sets:
+            if value == "half":
+                s["mask"].fill_(0.0)
+                s["mask"][:, :v // 2] = 1.0
+            elif value is not None:
+                s["mask"].fill_(value)
+
+    def window(value):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for k in range(a.launches):
+            s = sets[k % n_sets]
+            if value is None:
+                call("mi_ddim_step", ptr(s["x"]), ptr(s["mo"]), ptr(s["z"]), ptr(table), ptr(idx), ptr(s["x_cl"]), c, n, c, v, 1)
+            else:
+                call("mi_step_inpaint", ptr(s["x"]), ptr(s["mo"]), ptr(s["z"]), ptr(table), ptr(idx), None, ptr(s["mask"]), ptr(s["image"]),
+                     ptr(s["zk"]), ptr(known), ptr(s["x_cl"]), c, n, c, v, 1, 1)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / a.launches * 1e3  # microseconds per launch
+
+    times = {k: [] for k in variants}
+    for rep in range(a.repeats + 1):  # the first round warms up
+        for k, (value, _) in variants.items():
+            fill(value)
+            torch.cuda.synchronize()
+            t = window(value)
+            if rep:
+                times[k].append(t)
+    med = {k: statistics.median(t) for k, t in times.items()}
+    print(json.dumps(dict(measure="launch", config=name, shape=list(shape), launches=a.launches, sets=n_sets, repeats=a.repeats,
+                          us_per_launch={k: round(t, 2) for k, t in med.items()},
+                          us_min_max={k: [round(min(t), 2), round(max(t), 2)] for k, t in times.items()},
+                          bytes_per_element={k: round(b, 2) for k, (_, b) in variants.items()},
+                          gb_per_s={k: round(el * variants[k][1] / (med[k] * 1e-6) / 1e9, 1) for k in variants},
+                          over_plain={k: round(med[k] / med["mi_ddim_step"], 3) for k in variants})), flush=True)
+    del sets
+    torch.cuda.empty_cache()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--repeats", type=int, default=7)
+    ap.add_argument("--launches", type=int, default=96)
+    ap.add_argument("--footprint-mib", type=int, default=384)
+    ap.add_argument("--only", default=None)
+    ap.add_argument("--part", default="both", choices=("both", "loop", "launch"))
+    a = ap.parse_args()
+    import torch
+    import bench
+    torch.manual_seed(0)
+    c3b = dict(spatial_dims=3, in_channels=8, out_channels=8, num_res_blocks=2, num_channels=[256, 512, 768], attention_levels=[False, True, True],
+               num_head_channels=[0, 512, 768], norm_num_groups=32, strides=iso(3), kernel_sizes=[[3] * 3] * 3, paddings=[[1] * 3] * 3)
+    for name, kw, shape in (("c4", bench.C4, (1, 1, 128, 128, 128)), ("c3b", c3b, (4, 8, 32, 32, 32))):
+        if a.only in (None, name):
+            if a.part != "loop":
+                launches(name, shape, a)
+            if a.part != "launch":
+                loops(name, kw, shape, a)
+
+
+if __name__ == "__main__":
+    main()
