@@ -75,6 +75,12 @@ int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N,
               const float* scale_shift, const float* mean_rstd, int silu, const void* add, int add_cstride, const void* add2, int add2_cstride,
               void* dx, int dx_cstride, float* dgamma, float* dbeta, float* coef, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 
+/* The first two launches of mi_gn_bwd alone (partial sums, finalize): coef[N][C][3] = (a, b, c) of dx = a du + b x + c per (image,
+ * channel), dgamma / dbeta accumulated.  For callers that evaluate the apply pass themselves (mi_conv1x1_dgrad_gn_bwd). */
+int mi_gn_bwd_coef(const void* g, int g_cstride, const void* x, int x_cstride, int N, int64_t V, int C, int G, const float* gamma,
+                   const float* scale_shift, const float* mean_rstd, int silu, float* dgamma, float* dbeta, float* coef, void* workspace,
+                   int64_t workspace_bytes, hipStream_t stream);
+
 /* mi_gn_bwd in two launches instead of three: the partial pass adds its block totals (sum du, sum du x per channel) to `sums_zeroed`
  * -- [N][C][2] fp64, ZERO on entry (the caller takes it from a buffer it clears once per step) -- with hardware fp64 atomics, and the
  * apply pass derives the per-(image, group) coefficients and the gamma / beta gradients from those sums itself: no finalize launch in
@@ -126,6 +132,23 @@ int mi_conv_dgrad(mi_conv_plan* plan, const void* dy, int dy_cstride, void* dx, 
  * batch into one row (= the bias gradient) */
 int mi_conv_wgrad(mi_conv_plan* plan, const void* x, int x_cstride, const void* dy, int dy_cstride, float* dweight, float* dy_colsum,
                   int dy_colsum_stride, hipStream_t stream);
+/* ---- ResnetBlock skip conv (1x1, Cin != Cout; UNet:664-672) sharing its passes over x with norm1 + SiLU of the block (UNet:628-629):
+ * the streaming 1x1 kernel (conv1x1.hip) also does norm1's elementwise work, so x is read once in forward and the skip conv's data
+ * gradient never reaches memory in backward.  Results equal the unfused sequences bit for bit (tests/test_skip_fuse_gpu.py).
+ * mi_conv1x1_skip_fusable(dir, ...): 1 when the kernel covers the shape (dir 1: forward, 2: backward; Cin / Cout of the skip conv), without
+ * launching; the entry points return MI_ERR_UNSUPPORTED otherwise, for voxel pitches that are no multiple of 8 and for a plan whose
+ * forward / data gradient does not run on the streaming kernel.
+ * fwd:  y = W x + addvec (as mi_conv_fwd) and a1 = silu(scale x + shift) (as mi_gn_apply with norm1's scale_shift [N][Cin][2]).
+ * bwd:  dx = mi_gn_bwd(g, x, ..., add = add2, add2 = mi_conv_dgrad(plan, dout)): the partial and finalize launches of mi_gn_bwd, then
+ *       the data-gradient kernel with the apply pass as its epilogue.  add2 (optional): the other pending branch of x's gradient. */
+int mi_conv1x1_skip_fusable(int dir, int N, int64_t V, int Cin, int Cout);
+int mi_conv1x1_fwd_gn_apply(mi_conv_plan* plan, const void* x, int x_cstride, const float* addvec, int addvec_stride, void* y, int y_cstride,
+                            const float* scale_shift, void* a1, int a1_cstride, int N, int64_t V, int Cin, int Cout, hipStream_t stream);
+int mi_conv1x1_dgrad_gn_bwd(mi_conv_plan* plan, const void* dout, int dout_cstride, const void* g, int g_cstride, const void* x,
+                            int x_cstride, int N, int64_t V, int Cin, int Cout, int G, const float* gamma, const float* scale_shift,
+                            const float* mean_rstd, const void* add2, int add2_cstride, void* dx, int dx_cstride, float* dgamma,
+                            float* dbeta, float* coef, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* Which kernel ran (tests): the id of the kernel family that the most recent mi_conv_fwd / mi_conv_dgrad / mi_conv_wgrad of the calling
  * thread launched -- a host-side thread_local stored at each launch site, one value per instantiation family the dispatch can reach.
  * An Upsample + conv plan on its fallback reports its inner plan's kernel.  Not a stream operation; nothing reads it on the hot path. */

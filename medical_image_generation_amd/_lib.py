@@ -33,6 +33,7 @@ _SIGS = {
     "mi_gn_stats_from_partial": [_p, _i, _i, _p, _i, _i, _i, _l, _i, _f, _p, _p, _p, _p, _p],
     "mi_gn_apply": [_p, _i, _p, _p, _i, _i, _l, _i, _i, _p],
     "mi_gn_bwd": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _l, _p],
+    "mi_gn_bwd_coef": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _l, _p],
     "mi_gn_bwd_fused": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p],
     "mi_conv_plan_create": [C.POINTER(_p), _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
     "mi_upconv_plan_create": [C.POINTER(_p), _i, _i, _i, _i, _i, _i],
@@ -47,6 +48,9 @@ _SIGS = {
     "mi_conv_last_kernel": [],
     "mi_conv_plan_wgrad_splits": [_p],
     "mi_conv_dgrad": [_p, _p, _i, _p, _i, _p],
+    "mi_conv1x1_skip_fusable": [_i, _i, _l, _i, _i],
+    "mi_conv1x1_fwd_gn_apply": [_p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _l, _i, _i, _p],
+    "mi_conv1x1_dgrad_gn_bwd": [_p, _p, _i, _p, _i, _p, _i, _i, _l, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _l, _p],
     "mi_conv_wgrad": [_p, _p, _i, _p, _i, _p, _p, _i, _p],
     "mi_linear_wgrad_bf16": [_p, _i, _i, _p, _i, _i, _l, _p, _p, _p],
     "mi_colsum_bf16": [_p, _p, _i, _i, _l, _i, _i, _p],
@@ -138,7 +142,7 @@ _SIGS = {
     "mi_kl_eval": [_p, _p, _p, _i, _i, _l, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l}
-_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
+_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_conv1x1_skip_fusable", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
             "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits"}
 
 _lib = None

@@ -42,6 +42,7 @@ class ResnetBlock(_Block):
         self.groups, self.eps = norm_num_groups, norm_eps
         self._mode = "up" if up else ("down" if down else None)
         self._stride, self._kernel = _axis3(stride, sd, 1), _axis3(kernel_size, sd, 1)
+        self.fuse_skip = None  # engine.resnet's fuse_skip (None: the engine's default route)
         spec = ParamSpec(self, sd)
         spec.norm("norm1", in_channels)
         spec.conv("conv1.conv", in_channels, self.out_channels, 3)
@@ -72,7 +73,7 @@ class ResnetBlock(_Block):
                 c.tape.record(bwd_emb)
             # a leading identity op so that the block input has a gradient slot even when it is only read by norm1 / the resamplers
             y = E.resnet(c, x_cl, "", self.spatial_dims, self.groups, self.eps, temb, d_temb, mode=self._mode, stride=self._stride,
-                         kernel=self._kernel)
+                         kernel=self._kernel, fuse_skip=self.fuse_skip)
             return (y,), {"x_cl": x_cl, "d_emb": lambda: state.get("d_emb")}
 
         return self._edge(runner, x, emb)

@@ -10,12 +10,55 @@
 #include <stdlib.h>
 
 #include "conv_common.h"
+#include "gn_elem.h"
 #include "medimgen_hip.h"
 
 namespace {
 
-template <int NCH>  // 32-channel input chunks (K = 32 * NCH)
-__global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vox_per_image, int stage) {
+// ResnetBlock skip conv (x -> xs = W_s x + b) sharing its pass over x with norm1 of the block, mode:
+//   1 (forward): the B fragments of x the kernel holds also leave as a1 = silu(scale * x + shift), the input of conv1 -- x is read once;
+//   2 (data gradient): the tile of d_skip = W_s^T dout is not stored; every 16-byte piece of it (rounded to bf16 as the stored tensor
+//     was) goes in as the `add` branch of norm1's backward apply, evaluated here: dx = a du + b x + c (+ add2) + d_skip.
+// The per-(image, channel) tables (scale_shift [N][C][2]; coef [N][C][3]) sit in LDS behind the store tiles; C = channels of x.
+struct SkipFuse {
+  int mode;
+  const float* scale_shift;
+  const float* coef;                 // mode 2
+  bf16* a1; int a1_cs; unsigned a1_bytes;  // mode 1
+  const bf16* g; int g_cs;           // mode 2: dL/d(a1)
+  const bf16* xn; int xn_cs;         // mode 2: x (the norm's input)
+  const bf16* add2; int add2_cs;     // mode 2: other pending branch of x's gradient (null: none); added BEFORE d_skip, as mi_gn_bwd's
+                                     // add comes before its add2 and the tape queues the skip gradient last
+  int N;
+  int tile_ch;                       // channels per row of the store tile (filled by the launcher)
+};
+thread_local const SkipFuse* t_fuse = nullptr;  // set by the fused entry points around mi_conv_fwd / mi_conv_dgrad, taken by mi_launch_conv1x1
+thread_local bool t_fuse_taken = false;
+
+// tile width of a fused launch: mode 1 -- a1 slabs (all chunks up to 3, else half of them) and xs; mode 2 -- three cout blocks of d_skip
+inline int fused_tile_ch(int mode, int Cin, int Cout) {
+  if (mode == 1) {
+    const int nch = (Cin + 31) / 32, slab = nch <= 3 ? Cin : (nch / 2) * 32;
+    return slab > Cout ? slab : Cout;
+  }
+  return Cout < 96 ? Cout : 96;
+}
+// LDS bytes of a fused launch: weights, 4 wave tiles, norm1's tables over all N images.  C = channels of x
+inline size_t fused_lds(int mode, int nfrags, int tile_ch, int N, int C) {
+  return (size_t)nfrags * 1024 + (size_t)4 * 32 * (tile_ch * 2 + 16) + (size_t)N * C * (mode == 2 ? 5 : 2) * sizeof(float);
+}
+constexpr size_t kFusedLdsMax = 64 * 1024;  // (as for the staged stores of the plain kernel: two workgroups per CU at least)
+
+// image of voxel v0 + row, given image n0 / remainder rem0 of v0: no 64-bit division per lane
+__device__ __forceinline__ int image_of(int n0, int64_t rem0, int row, int64_t vpi) {
+  int64_t rem = rem0 + row;
+  int n = n0;
+  while (rem >= vpi) { rem -= vpi; ++n; }
+  return n;
+}
+
+template <int NCH, int FUSE>  // 32-channel input chunks (K = 32 * NCH); FUSE = SkipFuse::mode (0: plain conv, `f` unused)
+__global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, SkipFuse f, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vox_per_image, int stage) {
   constexpr int K16 = 2 * NCH;
   extern __shared__ __attribute__((aligned(16))) char lds[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -23,11 +66,23 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int 
   // (consecutive lanes = consecutive bytes of a voxel, then the next voxel).  Straight from the accumulators a store instruction
   // writes 64 separate 16-byte fragments (lane = (voxel, half), 32 bytes apart, voxel pitch = Cout * 2): measured 2.8 TB/s on the
   // write-heavy 32 -> 96 data gradient of a skip conv where the forward direction (96 -> 32) streams at 5.1.
-  const int tile_pitch = a.Cout * 2 + 16;  // bytes per voxel row of the tile (+16: rows start 4 banks apart)
+  // fused forms: the tile is at most 96 channels wide (a 192-channel tile per wave would leave one workgroup per CU) -- a1 passes
+  // through it in one or two slabs of input chunks before xs does, d_skip in slabs of three cout blocks
+  const int tile_ch = FUSE != 0 ? f.tile_ch : a.Cout;
+  const int tile_pitch = tile_ch * 2 + 16;  // bytes per voxel row of the tile (+16: rows start 4 banks apart)
   char* tile = lds + (size_t)nfrags * 1024 + (size_t)wave * 32 * tile_pitch;
   const int r = lane & 31, h = lane >> 5;
   // packed fragments -> LDS, same order: [cout group y][chunk][ks][cb], 1 KiB each
   for (int i = threadIdx.x; i < nfrags * 64; i += 256) ((u32x4*)lds)[i] = a.wpk[i];
+  // fused forms: norm1's tables behind the tiles, [N][C][2] scale / shift (+ [N][C][3] backward coefficients)
+  const int fC = FUSE == 1 ? a.Cin : a.Cout;  // channels of x
+  const float* tab_ss = (const float*)(lds + (size_t)nfrags * 1024 + (size_t)4 * 32 * tile_pitch);
+  const float* tab_cf = tab_ss + (size_t)f.N * fC * 2;
+  if constexpr (FUSE != 0) {
+    for (int i = threadIdx.x; i < f.N * fC * 2; i += 256) const_cast<float*>(tab_ss)[i] = f.scale_shift[i];
+    if constexpr (FUSE == 2)
+      for (int i = threadIdx.x; i < f.N * fC * 3; i += 256) const_cast<float*>(tab_cf)[i] = f.coef[i];
+  }
   __syncthreads();
   const __amdgpu_buffer_rsrc_t rx = make_rsrc(a.x, a.x_bytes);
   const __amdgpu_buffer_rsrc_t ry = make_rsrc(a.y, a.y_bytes);
@@ -51,7 +106,43 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int 
     if (blk + bstep < nblocks) load_block(bnext, blk + bstep);  // in flight under this block's MFMAs and stores
     const int64_t v = blk * 32 + r;
     const int64_t n = v / vox_per_image;
-    for (int c32 = 0; c32 < ncb_total; ++c32) {
+    if constexpr (FUSE == 1) {  // a1 = silu(scale x + shift) from the fragments in registers: every channel once, whatever the cout blocks
+      const __amdgpu_buffer_rsrc_t ra1 = make_rsrc(f.a1, f.a1_bytes);
+      const int64_t v0 = blk * 32;
+      constexpr int KS = NCH <= 3 ? K16 : K16 / 2;  // k-steps per slab: all chunks, or half of 4 / 6
+#pragma unroll
+      for (int s = 0; s < K16 / KS; ++s) {
+        const int cb0 = s * KS * 16;
+        if (v < nvox) {
+#pragma unroll
+          for (int k2 = 0; k2 < KS; ++k2) {
+            const int kk = s * KS + k2, c = kk * 16 + 8 * h;
+            if (c + 8 <= a.Cin) {
+              const f32x4* t = (const f32x4*)(tab_ss + ((size_t)n * a.Cin + c) * 2);
+              const f32x4 t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+              const float sc[8] = {t0[0], t0[2], t1[0], t1[2], t2[0], t2[2], t3[0], t3[2]};
+              const float sh[8] = {t0[1], t0[3], t1[1], t1[3], t2[1], t2[3], t3[1], t3[3]};
+              F8 fx = unpack8(bcur[kk]);
+#pragma unroll
+              for (int j = 0; j < 8; ++j) fx.v[j] = gn_apply_elem<1>(fx.v[j], sc[j], sh[j]);
+              *(u32x4*)(tile + r * tile_pitch + (c - cb0) * 2) = pack8(fx);
+            }
+          }
+        }
+        const int ws = a.Cin - cb0 < KS * 16 ? a.Cin - cb0 : KS * 16;  // channels of this slab
+        const int ppv = ws >> 3;
+        for (int i = lane; i < 32 * ppv; i += 64) {
+          const int row = i / ppv, col = i - row * ppv;
+          const u32x4 piece = *(const u32x4*)(tile + row * tile_pitch + col * 16);
+          const unsigned off = (v0 + row < nvox) ? (unsigned)(((v0 + row) * f.a1_cs + cb0 + col * 8) * 2) : 0xfffffff0u;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, piece), ra1, (int)off, 0, 0);
+        }
+      }
+    }
+    const int SB = FUSE == 2 ? 3 : ncb_total;  // cout blocks per pass through the tile
+    for (int s0 = 0; s0 < ncb_total; s0 += SB) {
+    const int s1 = s0 + SB < ncb_total ? s0 + SB : ncb_total;
+    for (int c32 = s0; c32 < s1; ++c32) {
       const int yg = c32 / NCB, cb = c32 - yg * NCB;
       const int co = c32 * 32 + 16 * h;
       f32x16 acc;
@@ -67,8 +158,8 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int 
 #pragma unroll
       for (int e = 0; e < 8; ++e) { lo.v[e] = acc[e]; hi.v[e] = acc[8 + e]; }
       if (stage) {
-        if (co + 8 <= a.Cout) *(u32x4*)(tile + r * tile_pitch + co * 2) = pack8(lo);
-        if (co + 16 <= a.Cout) *(u32x4*)(tile + r * tile_pitch + co * 2 + 16) = pack8(hi);
+        if (co + 8 <= a.Cout) *(u32x4*)(tile + r * tile_pitch + (co - s0 * 32) * 2) = pack8(lo);
+        if (co + 16 <= a.Cout) *(u32x4*)(tile + r * tile_pitch + (co - s0 * 32) * 2 + 16) = pack8(hi);
       } else if (vec_ok) {
         const bool in0 = (v < nvox) & (co + 8 <= a.Cout), in1 = (v < nvox) & (co + 16 <= a.Cout);
         const unsigned o0 = in0 ? (unsigned)((v * a.y_cs + co) * 2) : 0xfffffff0u;
@@ -82,7 +173,60 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int 
           if (co + e < a.Cout) yp[e] = f2bf(acc[e]);
       }
     }
-    if (stage) {  // (wave-private tile: this wave's LDS operations complete in order, no barrier)
+    if constexpr (FUSE == 2) {  // norm1's backward apply on this slab of the d_skip tile (launch: stage is on)
+      const int cb0 = s0 * 32;
+      const int ppv = (a.Cout - cb0 < SB * 32 ? a.Cout - cb0 : SB * 32) >> 3;
+      const int64_t v0 = blk * 32;
+      const int n0 = (int)(v0 / vox_per_image);
+      const int64_t rem0 = v0 - (int64_t)n0 * vox_per_image;
+      constexpr int U = 2;  // pieces in flight per stream, as in k_gn_bwd_apply
+      for (int i0 = lane; i0 < 32 * ppv; i0 += 64 * U) {
+        u32x4 rx[U], rg[U], ra2[U];
+        int rowk[U], colk[U];
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int i = i0 + 64 * k;
+          rowk[k] = i / ppv; colk[k] = i - rowk[k] * ppv;
+          const int64_t vk = v0 + rowk[k];
+          if (i < 32 * ppv && vk < nvox) {
+            rx[k] = *(const u32x4*)(f.xn + vk * f.xn_cs + cb0 + colk[k] * 8);
+            rg[k] = __builtin_nontemporal_load((const u32x4*)(f.g + vk * f.g_cs + cb0 + colk[k] * 8));
+            if (f.add2) ra2[k] = __builtin_nontemporal_load((const u32x4*)(f.add2 + vk * f.add2_cs + cb0 + colk[k] * 8));
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+          const int i = i0 + 64 * k;
+          const int64_t vk = v0 + rowk[k];
+          if (i >= 32 * ppv || vk >= nvox) break;
+          const int ni = image_of(n0, rem0, rowk[k], vox_per_image);
+          const size_t ch = (size_t)ni * a.Cout + cb0 + colk[k] * 8;
+          const f32x4* t = (const f32x4*)(tab_ss + ch * 2);
+          const f32x4 t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
+          const float sc[8] = {t0[0], t0[2], t1[0], t1[2], t2[0], t2[2], t3[0], t3[2]};
+          const float sh[8] = {t0[1], t0[3], t1[1], t1[3], t2[1], t2[3], t3[1], t3[3]};
+          float cf[24];  // (a, b, c) of the octet's channels: 96 contiguous, 16-byte aligned bytes
+#pragma unroll
+          for (int q = 0; q < 6; ++q) {
+            const f32x4 tq = ((const f32x4*)(tab_cf + ch * 3))[q];
+            cf[4 * q] = tq[0]; cf[4 * q + 1] = tq[1]; cf[4 * q + 2] = tq[2]; cf[4 * q + 3] = tq[3];
+          }
+          const F8 fs = unpack8(*(const u32x4*)(tile + rowk[k] * tile_pitch + colk[k] * 16));  // d_skip, bf16-rounded
+          const F8 fx = unpack8(rx[k]), fg = unpack8(rg[k]);
+          F8 o;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o.v[j] = gn_bwd_elem<1>(fg.v[j], fx.v[j], sc[j], sh[j], cf[3 * j], cf[3 * j + 1], cf[3 * j + 2]);
+          if (f.add2) {
+            const F8 fa = unpack8(ra2[k]);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) o.v[j] += fa.v[j];
+          }
+#pragma unroll
+          for (int j = 0; j < 8; ++j) o.v[j] += fs.v[j];
+          __builtin_nontemporal_store(pack8(o), (u32x4*)(a.y + vk * a.y_cs + cb0 + colk[k] * 8));
+        }
+      }
+    } else if (stage) {  // (wave-private tile: this wave's LDS operations complete in order, no barrier)
       const int ppv = a.Cout >> 3;  // 16-byte pieces per voxel
       const int64_t v0 = blk * 32;
       for (int i = lane; i < 32 * ppv; i += 64) {
@@ -92,19 +236,27 @@ __global__ void __launch_bounds__(256) k_conv1x1(ConvArgs a, int ncb_total, int 
         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, piece), ry, (int)off, 0, 0);
       }
     }
+    }  // slabs of cout blocks
 #pragma unroll
     for (int kk = 0; kk < K16; ++kk) bcur[kk] = bnext[kk];
   }
 }
 
-template <int NCH>
-int launch11(const ConvArgs& a, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vpi, hipStream_t st) {
+template <int NCH, int FUSE>
+int launch11(const ConvArgs& a, SkipFuse f, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vpi, hipStream_t st) {
   size_t lds = (size_t)nfrags * 1024;
   // staged stores (see the kernel): whole channel octets, 16-byte aligned pitch, a tile per wave that fits beside the weights
   const size_t tile_bytes = (size_t)4 * 32 * (a.Cout * 2 + 16);
-  const int stage = (a.y_cs & 7) == 0 && (a.Cout & 7) == 0 && a.y_bytes != 0 && a.Cout >= 16 && lds + tile_bytes <= 64 * 1024;
-  if (stage) lds += tile_bytes;
-  auto kern = k_conv1x1<NCH>;
+  int stage = (a.y_cs & 7) == 0 && (a.Cout & 7) == 0 && a.y_bytes != 0 && a.Cout >= 16 && lds + tile_bytes <= 64 * 1024;
+  if (FUSE != 0) {  // the fused forms need the tile (and its staged xs / d_skip): refuse what the plain kernel would store directly
+    f.tile_ch = fused_tile_ch(FUSE, a.Cin, a.Cout);
+    stage = (a.y_cs & 7) == 0 && (a.Cout & 7) == 0 && a.y_bytes != 0 && a.Cout >= 16;
+    lds = fused_lds(FUSE, nfrags, f.tile_ch, f.N, FUSE == 1 ? a.Cin : a.Cout);
+    if (!stage || lds > kFusedLdsMax) return MI_ERR_UNSUPPORTED;
+  } else if (stage) {
+    lds += tile_bytes;
+  }
+  auto kern = k_conv1x1<NCH, FUSE>;
   static bool attr_set = false;
   if (!attr_set) {
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -115,9 +267,21 @@ int launch11(const ConvArgs& a, int ncb_total, int NCB, int nfrags, int64_t nvox
   int grid = (int)((nblocks + 3) / 4);
   if (grid > 256 * 6) grid = 256 * 6;  // ~6 workgroups (24 waves) per CU keep enough loads in flight
   if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, ncb_total, NCB, nfrags, nvox, vpi, stage);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, f, ncb_total, NCB, nfrags, nvox, vpi, stage);
   MI_CHECK_LAUNCH();
   return 0;
+}
+
+template <int FUSE>
+int launch11_nch(const ConvArgs& a, const SkipFuse& f, int nch, int ncb_total, int NCB, int nfrags, int64_t nvox, int64_t vpi, hipStream_t st) {
+  switch (nch) {
+    case 1: return launch11<1, FUSE>(a, f, ncb_total, NCB, nfrags, nvox, vpi, st);
+    case 2: return launch11<2, FUSE>(a, f, ncb_total, NCB, nfrags, nvox, vpi, st);
+    case 3: return launch11<3, FUSE>(a, f, ncb_total, NCB, nfrags, nvox, vpi, st);
+    case 4: return launch11<4, FUSE>(a, f, ncb_total, NCB, nfrags, nvox, vpi, st);
+    case 6: return launch11<6, FUSE>(a, f, ncb_total, NCB, nfrags, nvox, vpi, st);
+    default: return MI_ERR_UNSUPPORTED;
+  }
 }
 
 }  // namespace
@@ -132,15 +296,86 @@ int mi_launch_conv1x1(const ConvArgs& a, int NCB, int ny, hipStream_t st) {
   const int64_t vpi = (int64_t)a.Do * a.Ho * a.Wo, nvox = vpi * a.N;
   const int ncb_total = (a.Cout + 31) / 32;
   mi_conv_note_kernel(MI_CK_1X1_STREAM);
-  switch (nch) {
-    case 1: return launch11<1>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
-    case 2: return launch11<2>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
-    case 3: return launch11<3>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
-    case 4: return launch11<4>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
-    case 6: return launch11<6>(a, ncb_total, NCB, nfrags, nvox, vpi, st);
-    default: return MI_ERR_UNSUPPORTED;
+  if (t_fuse) {  // a fused entry point below is the caller of the plan call that got here
+    const SkipFuse f = *t_fuse;
+    t_fuse_taken = true;
+    if (f.N != a.N) return MI_ERR_BAD_ARG;
+    return f.mode == 1 ? launch11_nch<1>(a, f, nch, ncb_total, NCB, nfrags, nvox, vpi, st)
+                       : launch11_nch<2>(a, f, nch, ncb_total, NCB, nfrags, nvox, vpi, st);
   }
+  return launch11_nch<0>(a, SkipFuse{}, nch, ncb_total, NCB, nfrags, nvox, vpi, st);
 }
+
+namespace {
+// the plan call of a fused entry point: hands `f` to mi_launch_conv1x1; a plan that takes another route has run its plain conv
+template <class Call>
+int with_fuse(const SkipFuse& f, Call call) {
+  t_fuse = &f;
+  t_fuse_taken = false;
+  const int e = call();
+  t_fuse = nullptr;
+  if (e) return e;
+  return t_fuse_taken ? 0 : MI_ERR_UNSUPPORTED;
+}
+inline unsigned span_bytes(int N, int64_t V, int cs) {
+  const int64_t b = (int64_t)N * V * cs * 2;
+  return b < (1ll << 32) - 16 ? (unsigned)b : 0u;
+}
+}  // namespace
+
+extern "C" {
+
+// Shapes the two entry points below cover (the structural limits of k_conv1x1's fused forms; the plan must also route to it, which
+// plans do at these shapes unless MI_CONV1X1=0): dir 1 forward, 2 data gradient.  Cin / Cout: the skip conv's.
+int mi_conv1x1_skip_fusable(int dir, int N, int64_t V, int Cin, int Cout) {
+  if (N <= 0 || V <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 7) || (Cout & 7) || Cin < 16 || Cout < 16) return 0;
+  const int K = dir == 1 ? Cin : Cout, M = dir == 1 ? Cout : Cin;  // channels the loader reads / the kernel produces
+  const int nch = (K + 31) / 32, ncb = (M + 31) / 32;
+  if (!(nch == 1 || nch == 2 || nch == 3 || nch == 4 || nch == 6)) return 0;
+  if (((Cout + 31) / 32) * ((Cin + 31) / 32) * 2 > 96) return 0;
+  const int nfrags = ((ncb + 1) & ~1) * nch * 2;  // (cout blocks come packed in groups of one or two)
+  if ((int64_t)N * V * (Cin > Cout ? Cin : Cout) * 2 >= (1ll << 32) - 16) return 0;  // dense tensors within a buffer descriptor
+  return fused_lds(dir, nfrags, fused_tile_ch(dir, K, M), N, Cin) <= kFusedLdsMax ? 1 : 0;
+}
+
+// Forward of a ResnetBlock skip conv that also emits conv1's input: y = W x + addvec as mi_conv_fwd, and a1 = silu(scale x + shift)
+// with norm1's scale_shift [N][Cin][2] -- the tensor mi_gn_apply(x, ..., silu = 1) writes, bit for bit -- in the same pass over x.
+// MI_ERR_UNSUPPORTED where mi_conv1x1_skip_fusable says 0, for pitches that are no multiple of 8, and for plans that do not run the
+// streaming 1x1 kernel.
+int mi_conv1x1_fwd_gn_apply(mi_conv_plan* plan, const void* x, int x_cstride, const float* addvec, int addvec_stride, void* y, int y_cstride,
+                            const float* scale_shift, void* a1, int a1_cstride, int N, int64_t V, int Cin, int Cout, hipStream_t st) {
+  if (!plan || !x || !y || !scale_shift || !a1 || a1_cstride < Cin || x_cstride < Cin || y_cstride < Cout) return MI_ERR_BAD_ARG;
+  if ((x_cstride & 7) || (y_cstride & 7) || (a1_cstride & 7) || !mi_conv1x1_skip_fusable(1, N, V, Cin, Cout)) return MI_ERR_UNSUPPORTED;
+  SkipFuse f{};
+  f.mode = 1; f.scale_shift = scale_shift; f.a1 = (bf16*)a1; f.a1_cs = a1_cstride; f.a1_bytes = span_bytes(N, V, a1_cstride); f.N = N;
+  if (!f.a1_bytes || !span_bytes(N, V, x_cstride) || !span_bytes(N, V, y_cstride)) return MI_ERR_UNSUPPORTED;
+  return with_fuse(f, [&] { return mi_conv_fwd(plan, x, x_cstride, addvec, addvec_stride, nullptr, 0, y, y_cstride, nullptr, st); });
+}
+
+// Backward of the pair (skip conv, norm1 + SiLU) w.r.t. their common input x: mi_gn_bwd(g, x, ..., add = add2, add2 = d_skip) with
+// d_skip = mi_conv_dgrad(plan, dout) computed tile by tile inside the apply pass and never stored -- same dx, bit for bit.  Launches
+// mi_gn_bwd's partial and finalize kernels unchanged (dgamma / dbeta accumulated, coef written), then the 1x1 data-gradient kernel with
+// the apply as its epilogue.  add2: the other pending branch of x's gradient (own pitch) or null.  C = channels of x = the conv's Cin.
+int mi_conv1x1_dgrad_gn_bwd(mi_conv_plan* plan, const void* dout, int dout_cstride, const void* g, int g_cstride, const void* x,
+                            int x_cstride, int N, int64_t V, int Cin, int Cout, int G, const float* gamma, const float* scale_shift,
+                            const float* mean_rstd, const void* add2, int add2_cstride, void* dx, int dx_cstride, float* dgamma,
+                            float* dbeta, float* coef, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  if (!plan || !dout || !g || !x || !dx || !gamma || !scale_shift || !mean_rstd || !coef || dout_cstride < Cout || g_cstride < Cin ||
+      x_cstride < Cin || dx_cstride < Cin || (add2 && add2_cstride < Cin))
+    return MI_ERR_BAD_ARG;
+  if ((dout_cstride & 7) || (g_cstride & 7) || (x_cstride & 7) || (dx_cstride & 7) || (add2 && (add2_cstride & 7)) ||
+      !mi_conv1x1_skip_fusable(2, N, V, Cin, Cout) || !span_bytes(N, V, dout_cstride) || !span_bytes(N, V, dx_cstride))
+    return MI_ERR_UNSUPPORTED;
+  if (int e = mi_gn_bwd_coef(g, g_cstride, x, x_cstride, N, V, Cin, G, gamma, scale_shift, mean_rstd, 1, dgamma, dbeta, coef, workspace,
+                             workspace_bytes, st))
+    return e;
+  SkipFuse f{};
+  f.mode = 2; f.scale_shift = scale_shift; f.coef = coef; f.g = (const bf16*)g; f.g_cs = g_cstride; f.xn = (const bf16*)x; f.xn_cs = x_cstride;
+  f.add2 = (const bf16*)add2; f.add2_cs = add2_cstride; f.N = N;
+  return with_fuse(f, [&] { return mi_conv_dgrad(plan, dout, dout_cstride, dx, dx_cstride, st); });
+}
+
+}  // extern "C"
 
 // ------------------------------------------------------------------------------------------------ 1x1x1 weight gradient
 // dW[co][ci] += sum_v dy[v][co] * x[v][ci]  (+ optional column sums of dy = bias gradient).  Also HBM-bound: x and dy are read

@@ -10,25 +10,12 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gn_elem.h"
 #include "medimgen_hip.h"
 
 namespace {
 
 constexpr int kT = 256;
-
-// activation behind the affine: 0 none, 1 SiLU (UNet / AEKL), 2 LeakyReLU(0.2) (the PatchDiscriminator's BatchNorm layers)
-template <int ACT>
-__device__ __forceinline__ float act_f(float u) {
-  if constexpr (ACT == 1) return silu_f(u);
-  else if constexpr (ACT == 2) return u > 0.f ? u : 0.2f * u;
-  else return u;
-}
-template <int ACT>
-__device__ __forceinline__ float act_grad_f(float u) {
-  if constexpr (ACT == 1) return silu_grad_f(u);
-  else if constexpr (ACT == 2) return u > 0.f ? 1.f : 0.2f;
-  else return 1.f;
-}
 
 struct Geo {
   int C8;    // channel groups of 8
@@ -214,10 +201,7 @@ __global__ void __launch_bounds__(kT) k_gn_apply(const bf16* __restrict__ x, int
       if (v + k * (int64_t)R >= V) break;
       F8 f = unpack8(raw[k]);
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float u = f.v[j] * sc[j] + sh[j];
-        f.v[j] = act_f<ACT>(u);
-      }
+      for (int j = 0; j < 8; ++j) f.v[j] = gn_apply_elem<ACT>(f.v[j], sc[j], sh[j]);
       *(u32x4*)(yb + (v + k * (int64_t)R) * ycs) = pack8(f);
     }
   }
@@ -435,11 +419,7 @@ __global__ void __launch_bounds__(kT) k_gn_bwd_apply(const bf16* __restrict__ g,
       if (vk >= V) break;
       F8 fx = unpack8(rx[k]), fg = unpack8(rg[k]), o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        float du = fg.v[j];
-        if (ACT) du *= act_grad_f<ACT>(fx.v[j] * sc[j] + sh[j]);
-        o.v[j] = ca[j] * du + cb[j] * fx.v[j] + cc[j];
-      }
+      for (int j = 0; j < 8; ++j) o.v[j] = gn_bwd_elem<ACT>(fg.v[j], fx.v[j], sc[j], sh[j], ca[j], cb[j], cc[j]);
       if (ab) {
         F8 fa = unpack8(ra[k]);
 #pragma unroll
@@ -641,12 +621,11 @@ int mi_gn_small_fwd(const void* x, int x_cstride, void* y, int y_cstride, int N,
   return 0;
 }
 
-int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N, int64_t V, int C, int G, const float* gamma,
-              const float* scale_shift, const float* mean_rstd, int silu, const void* add, int add_cstride, const void* add2, int add2_cstride,
-              void* dx, int dx_cstride, float* dgamma, float* dbeta, float* coef, void* workspace, int64_t workspace_bytes, hipStream_t st) {
-  if (bad_c(C, G) || N <= 0 || V <= 0 || (x_cstride & 7) || (g_cstride & 7) || (dx_cstride & 7) || (add && (add_cstride & 7)) ||
-      (add2 && (!add || (add2_cstride & 7))))
-    return MI_ERR_BAD_ARG;
+// the two launches in front of the backward's apply pass: partial sums, then the per-(n, channel) coefficients and dgamma / dbeta
+int mi_gn_bwd_coef(const void* g, int g_cstride, const void* x, int x_cstride, int N, int64_t V, int C, int G, const float* gamma,
+                   const float* scale_shift, const float* mean_rstd, int silu, float* dgamma, float* dbeta, float* coef, void* workspace,
+                   int64_t workspace_bytes, hipStream_t st) {
+  if (bad_c(C, G) || N <= 0 || V <= 0 || (x_cstride & 7) || (g_cstride & 7) || !coef) return MI_ERR_BAD_ARG;
   if (workspace_bytes < mi_gn_workspace_bytes(N, V, C)) return MI_ERR_BAD_ARG;
   int64_t vc = pick_vchunk(V);
   int chunks = (int)((V + vc - 1) / vc);
@@ -657,6 +636,19 @@ int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N,
                      x_cstride, scale_shift, (float*)workspace, C, V, vc, (double*)nullptr, 1);
   hipLaunchKernelGGL(k_gn_bwd_finalize, dim3(N * G), dim3(256), sizeof(float) * 2 * (size_t)(C / G), st, (const float*)workspace, chunks, C,
                      G, V, gamma, mean_rstd, coef, dgamma, dbeta);
+  MI_CHECK_LAUNCH();
+  return 0;
+}
+
+int mi_gn_bwd(const void* g, int g_cstride, const void* x, int x_cstride, int N, int64_t V, int C, int G, const float* gamma,
+              const float* scale_shift, const float* mean_rstd, int silu, const void* add, int add_cstride, const void* add2, int add2_cstride,
+              void* dx, int dx_cstride, float* dgamma, float* dbeta, float* coef, void* workspace, int64_t workspace_bytes, hipStream_t st) {
+  if (bad_c(C, G) || N <= 0 || V <= 0 || (x_cstride & 7) || (g_cstride & 7) || (dx_cstride & 7) || (add && (add_cstride & 7)) ||
+      (add2 && (!add || (add2_cstride & 7))))
+    return MI_ERR_BAD_ARG;
+  if (int e = mi_gn_bwd_coef(g, g_cstride, x, x_cstride, N, V, C, G, gamma, scale_shift, mean_rstd, silu, dgamma, dbeta, coef, workspace,
+                             workspace_bytes, st))
+    return e;
   int64_t grid = apply_grid(V * (C / 8), C / 8, N);
   // k_gn_bwd_apply keeps 2 pieces in flight per stream and uses non-temporal loads (g, the pending gradient branches) and stores (dx).
   // Measured round 3, same box, interleaved (profiles/r03i_ab_gn_variant.log), pieces in flight / non-temporal: 22.96 ms/step with 2 / no,

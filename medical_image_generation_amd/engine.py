@@ -224,6 +224,8 @@ def gn(ctx: Ctx, x, name, groups, eps):
 # Upsample (nearest x2 on all three axes) + k3 p1 conv as ONE op on the phase kernels (csrc/convph.hip: 8 taps per output voxel on
 # the coarse tensor instead of 27 on an up-sampled copy); MI_UPCONV=0: upsample kernel, then the plain conv (A/B runs).
 UPCONV = _os.environ.get("MI_UPCONV", "1") == "1"
+# MI_CONV1X1=0 (A/B runs) takes 1x1 convs off the streaming kernel, and with it the skip conv's fused forms (resnet)
+SKIP_STREAM = _os.environ.get("MI_CONV1X1", "1") != "0"
 
 
 def upsample_conv(ctx: Ctx, x, name, factors, kernel, padding, out=None):
@@ -280,28 +282,41 @@ def conv_transpose(ctx: Ctx, x, name, kernel, stride, padding):
     return y
 
 
+def _conv_plan(ctx: Ctx, x, name, kernel, stride, padding, upconv=False):
+    """The conv's plan for this input shape, its weights packed for this pass."""
+    n, d, h, w, cin = x.shape
+    wt = ctx.p(name + ".weight")
+    key = (name, n, d, h, w)
+    plan = ctx.plans.get(key)
+    if plan is None:
+        plan = ctx.plans[key] = ops.UpConvPlan(n, (d, h, w), cin, wt.shape[0]) if upconv else ops.ConvPlan(n, (d, h, w), cin, wt.shape[0], kernel, stride, padding)
+    if key not in ctx.packed:
+        plan.pack(wt)  # [Cout, Cin, (kd,) kh, kw] contiguous: same memory layout for 2-D and 3-D nets
+        ctx.packed.add(key)
+    return plan
+
+
 def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addvec=None, res=None, d_addvec=None,
-         need_dx=True, bias_grad_like=None, out=None, upconv=False):
+         need_dx=True, bias_grad_like=None, out=None, upconv=False, xin=None, y=None, skip=None, park=None):
     """y = conv(act(x)) + addvec + res   (weight `name.weight`, bias folded into addvec by the caller or taken from
     `name.bias` when addvec is None).  norm: GNStats of x, applied (+ SiLU) by one gn_apply pass in front of the conv.
     d_addvec: fp32 [N, Cout] view that receives the per-sample column sums of dy (time-embedding gradient) in backward.
     bias_grad_like: name of a conv whose output gradient is THIS conv's output gradient (a shortcut conv added as `res` of
-    that conv): its bias gradient, already computed when this backward runs, is copied instead of reducing dy a second time."""
+    that conv): its bias gradient, already computed when this backward runs, is copied instead of reducing dy a second time.
+    The ResnetBlock skip conv fused with norm1 (resnet(); csrc/conv1x1.hip) uses four more arguments.  On conv1: xin = act(norm(x)) as
+    the skip conv's forward already produced it (no gn_apply pass here); skip = the cell in which the skip conv's backward parks its
+    output gradient, so that the norm's backward computes the skip conv's data gradient on the fly.  On the skip conv: y = its output,
+    already computed; park = that cell (its backward then runs the weight gradient only)."""
     n, d, h, w, cin = x.shape
-    wt = ctx.p(name + ".weight")
-    cout = wt.shape[0]
-    key = (name, n, d, h, w)
-    plan = ctx.plans.get(key)
-    if plan is None:
-        plan = ctx.plans[key] = ops.UpConvPlan(n, (d, h, w), cin, cout) if upconv else ops.ConvPlan(n, (d, h, w), cin, cout, kernel, stride, padding)
-    if key not in ctx.packed:
-        plan.pack(wt)  # [Cout, Cin, (kd,) kh, kw] contiguous: same memory layout for 2-D and 3-D nets
-        ctx.packed.add(key)
+    cout = ctx.p(name + ".weight").shape[0]
+    plan = _conv_plan(ctx, x, name, kernel, stride, padding, upconv)
     av = addvec if addvec is not None else ctx.p(name + ".bias")
-    xin = ops.gn_apply(x, norm, silu) if norm is not None else x
-    y, sums = plan.fwd(xin, addvec=av, res=res, out=out, want_sums=True)  # out: channel-slice view of the consumer's concat buffer
-    if sums is not None:
-        ctx.sums[id(y)] = (sums, weakref.ref(y))
+    if xin is None:
+        xin = ops.gn_apply(x, norm, silu) if norm is not None else x
+    if y is None:
+        y, sums = plan.fwd(xin, addvec=av, res=res, out=out, want_sums=True)  # out: channel-slice view of the consumer's concat buffer
+        if sums is not None:
+            ctx.sums[id(y)] = (sums, weakref.ref(y))
     ctx.count(2 * y.numel() * cin * math.prod(kernel), dgrad=need_dx)
     if ctx.tape is not None:
         tape = ctx.tape
@@ -309,6 +324,8 @@ def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addv
         def bwd():
             dy = tape.take(y)
             if dy is None:
+                if skip is not None and "dout" in skip:  # nobody consumes the norm's backward: the parked skip gradient still counts
+                    tape.put(x, skip.pop("plan").dgrad(skip.pop("dout")))
                 return
             gw = ctx.g(name + ".weight")
             # column sums of dy come out of the wgrad kernel (one extra MFMA per k-step on the dY fragments it holds anyway):
@@ -321,12 +338,24 @@ def conv(ctx: Ctx, x, name, kernel, stride, padding, norm=None, silu=False, addv
                 plan.wgrad(xin, dy, gw, colsum=d_addvec if d_addvec is not None else ctx.g(name + ".bias"))
             if res is not None:
                 tape.put(res, dy)
-            if need_dx:
+            if park is not None:  # the data gradient is left to the backward of norm1, which runs next
+                park["dout"], park["plan"] = dy, plan
+            elif need_dx:
                 g = plan.dgrad(dy)
                 if norm is not None:
-                    other, other2 = tape.take2(x)
-                    dx = ops.gn_bwd(g, x, norm, ctx.p(norm.name + ".weight"), silu, ctx.g(norm.name + ".weight"),
-                                    ctx.g(norm.name + ".bias"), add=other, add2=other2)
+                    dout, splan = (skip.pop("dout", None), skip.pop("plan", None)) if skip is not None else (None, None)
+                    pending = tape.grads.get(id(x))
+                    if dout is not None and (isinstance(pending, tuple) or not ops.skip_fusable(2, splan, dout, g, x, pending)):
+                        tape.put(x, splan.dgrad(dout))  # a third branch, or pitches the kernel refuses: the skip gradient as a tensor
+                        dout = None
+                    if dout is not None:
+                        other = tape.take(x)
+                        dx = ops.conv1x1_dgrad_gn_bwd(splan, dout, g, x, norm, ctx.p(norm.name + ".weight"), ctx.g(norm.name + ".weight"),
+                                                      ctx.g(norm.name + ".bias"), add2=other)
+                    else:
+                        other, other2 = tape.take2(x)
+                        dx = ops.gn_bwd(g, x, norm, ctx.p(norm.name + ".weight"), silu, ctx.g(norm.name + ".weight"),
+                                        ctx.g(norm.name + ".bias"), add=other, add2=other2)
                     tape.grads[id(x)] = dx
                     tape.keep.append(x)
                 else:
@@ -440,16 +469,33 @@ def add(ctx: Ctx, a, b, b_needs_grad=True):
     return y
 
 
-def resnet(ctx: Ctx, x, name, sd, groups, eps, addvec, d_addvec, mode=None, stride=None, kernel=None, out=None):
+# The 1x1 skip conv of a ResnetBlock shares its passes over x with norm1 (csrc/conv1x1.hip): True (both directions), False, or "fwd" /
+# "bwd" (one of them: measurements).  resnet(fuse_skip=) overrides it per call (tests compare the routes).
+SKIP_FUSE = True
+
+
+def resnet(ctx: Ctx, x, name, sd, groups, eps, addvec, d_addvec, mode=None, stride=None, kernel=None, out=None, fuse_skip=None):
     """ResnetBlock.forward (UNet:674-701): 2 statistics passes (mostly from the producing convs' epilogues) + 3 fused convs.
     addvec: fp32 [N, Cout] = time_emb_proj(silu(emb)) + conv1.bias; d_addvec receives conv1's per-image dy column sums.
     mode: None | 'up' (nearest x stride) | 'down' (avg-pool kernel/stride): both x and act(norm1(x)) are resampled (UNet:679-687).
-    out: where conv2 writes the block's result (the first channels of the next skip-concat buffer)."""
+    out: where conv2 writes the block's result (the first channels of the next skip-concat buffer).
+    fuse_skip (default SKIP_FUSE): a block with a skip conv and no resampling runs the skip conv first -- its kernel reads x once and
+    also writes act(norm1(x)) for conv1 -- and in backward leaves the skip conv's data gradient to norm1's backward apply, where the
+    streaming 1x1 kernel covers the shape (ops.skip_fusable); every other block takes the separate passes."""
     k3, s1, p1 = (1,) * (3 - sd) + (3,) * sd, (1, 1, 1), (0,) * (3 - sd) + (1,) * sd
     name = name + "." if name else ""  # stand-alone blocks (blocks.ResnetBlock) have un-prefixed parameter names
     n1 = gn(ctx, x, name + "norm1", groups, eps)
+    has_skip = name + "skip_connection.conv.weight" in ctx.arena.offsets
+    fuse = SKIP_FUSE if fuse_skip is None else fuse_skip
+    xs = a1 = cell = None
+    if fuse and mode is None and has_skip and SKIP_STREAM and n1._pending is None:
+        splan = _conv_plan(ctx, x, name + "skip_connection.conv", (1, 1, 1), s1, (0, 0, 0))
+        if fuse in (True, "fwd") and ops.skip_fusable(1, splan, x):
+            xs, a1 = ops.conv1x1_fwd_gn_apply(splan, x, n1, ctx.p(name + "skip_connection.conv.bias"))
+        if fuse in (True, "bwd") and ctx.tape is not None and ops.skip_fusable(2, splan, x):
+            cell = {}
     if mode is None:
-        h = conv(ctx, x, name + "conv1.conv", k3, s1, p1, norm=n1, silu=True, addvec=addvec, d_addvec=d_addvec)
+        h = conv(ctx, x, name + "conv1.conv", k3, s1, p1, norm=n1, silu=True, addvec=addvec, d_addvec=d_addvec, xin=a1, skip=cell)
     else:
         h = gn_act(ctx, x, n1, True)
         if mode == "up":
@@ -458,8 +504,8 @@ def resnet(ctx: Ctx, x, name, sd, groups, eps, addvec, d_addvec, mode=None, stri
             x, h = avg_pool(ctx, x, kernel, stride), avg_pool(ctx, h, kernel, stride)
         h = conv(ctx, h, name + "conv1.conv", k3, s1, p1, addvec=addvec, d_addvec=d_addvec)
     n2 = gn(ctx, h, name + "norm2", groups, eps)
-    if name + "skip_connection.conv.weight" in ctx.arena.offsets:
-        xs = conv(ctx, x, name + "skip_connection.conv", (1, 1, 1), s1, (0, 0, 0), bias_grad_like=name + "conv2.conv")
+    if has_skip:  # (recorded here, behind conv1, whichever route: its backward runs before conv1's)
+        xs = conv(ctx, x, name + "skip_connection.conv", (1, 1, 1), s1, (0, 0, 0), bias_grad_like=name + "conv2.conv", y=xs, park=cell)
     else:
         xs = x
     return conv(ctx, h, name + "conv2.conv", k3, s1, p1, norm=n2, silu=True, res=xs, out=out)

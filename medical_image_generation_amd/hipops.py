@@ -326,6 +326,43 @@ class ConvPlan:
         call("mi_conv_wgrad", self.handle, ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(dweight_f32), ptr(colsum), cs_stride)
 
 
+# ----------------------------------------------------------------------------- skip 1x1 conv fused with norm1 (csrc/conv1x1.hip)
+def skip_fusable(direction, plan: ConvPlan, *tensors) -> bool:
+    """Does the streaming 1x1 kernel cover this skip conv's fused forward (direction 1) / backward (2)?  tensors: every activation the
+    call would be given (their voxel pitches must be multiples of 8 elements)."""
+    v = plan.dims[0] * plan.dims[1] * plan.dims[2]
+    # voxel pitches in whole octets; every tensor within the 4 GiB of a buffer descriptor
+    if plan.kernel != (1, 1, 1) or plan.stride != (1, 1, 1) or any(_cs(t) % 8 or plan.n * v * _cs(t) * 2 >= (1 << 32) - 16 for t in tensors if t is not None):
+        return False
+    return bool(_lib.call_raw("mi_conv1x1_skip_fusable", direction, plan.n, v, plan.cin, plan.cout))
+
+
+def conv1x1_fwd_gn_apply(plan: ConvPlan, x, st: GNStats, addvec=None):
+    """(xs, a1) = (plan.fwd(x, addvec), gn_apply(x, st, silu=True)) in one pass over x (mi_conv1x1_fwd_gn_apply)."""
+    n, v, c = _vox(x)
+    assert (n, tuple(x.shape[1:4]), c) == (plan.n, plan.dims, plan.cin) and (addvec is None or addvec.dim() == 1)
+    xs = torch.empty((n,) + plan.out_dims + (plan.cout,), dtype=BF16, device=x.device)
+    a1 = torch.empty(x.shape, dtype=BF16, device=x.device)
+    call("mi_conv1x1_fwd_gn_apply", plan.handle, ptr(x), _cs(x), ptr(addvec), 0, ptr(xs), plan.cout, ptr(st.scale_shift), ptr(a1), c, n, v,
+         plan.cin, plan.cout)
+    return xs, a1
+
+
+def conv1x1_dgrad_gn_bwd(plan: ConvPlan, dout, g, x, st: GNStats, gamma, dgamma, dbeta, add2=None):
+    """gn_bwd(g, x, st, gamma, True, dgamma, dbeta, add=add2, add2=plan.dgrad(dout)) without storing plan.dgrad(dout): the skip conv's data
+    gradient is the epilogue operand of norm1's backward apply (mi_conv1x1_dgrad_gn_bwd)."""
+    n, v, c = _vox(x)
+    assert c == plan.cin and dout.shape == (n,) + plan.out_dims + (plan.cout,)
+    dx = torch.empty(x.shape, dtype=BF16, device=x.device)
+    coef = torch.empty((n, c, 3), dtype=F32, device=x.device)
+    nb = _lib.call_raw("mi_gn_workspace_bytes", n, v, c)
+    ws = _workspace(nb, x.device)
+    call("mi_conv1x1_dgrad_gn_bwd", plan.handle, ptr(dout), _cs(dout), ptr(g), _cs(g), ptr(x), _cs(x), n, v, plan.cin, plan.cout, st.groups,
+         ptr(gamma), ptr(st.scale_shift), ptr(st.mean_rstd), ptr(add2), _cs(add2) if add2 is not None else 0, ptr(dx), c, ptr(dgamma),
+         ptr(dbeta), ptr(coef), ptr(ws), ws.numel())
+    return dx
+
+
 class UpConvPlan(ConvPlan):
     """Upsample.forward as one op (mi_upconv_plan_create): nearest x2 on all three axes, then the k3 s1 p1 conv; x is the COARSE
     tensor [N, D, H, W, Cin], y [N, 2D, 2H, 2W, Cout].  Same methods as ConvPlan (dgrad returns the coarse dx)."""
