@@ -47,7 +47,9 @@ __global__ void __launch_bounds__(256) k_layernorm_fwd(const bf16* __restrict__ 
 
 // dx = rstd * (g - mean(g) - xhat * mean(g * xhat)),  g = dy * gamma;  dgamma += sum_rows dy * xhat,  dbeta += sum_rows dy.
 // Each wave walks `rows_per_wave` rows keeping the per-channel sums of its pieces in registers; the four waves fold through LDS and
-// the block adds C x 2 values with fp32 atomics.
+// the block adds C x 2 values with fp32 atomics.  The dgamma terms dy * (x - mean) * rstd are formed and summed in fp64 and rounded once
+// per wave: in fp32 each term carries three roundings, which with a single row (M = 1) is more than the M * 2^-23 of the absolute sum the
+// result is held to (tests/gemm_ref.py); dx keeps the fp32 xhat.  The kernel stays bound by its three 2-byte streams.
 template <int NP>
 __global__ void __launch_bounds__(256) k_layernorm_bwd(const bf16* __restrict__ dy, int ldd, const bf16* __restrict__ x, int ldx,
                                                        const float* __restrict__ gamma, const float* __restrict__ mean_rstd, bf16* __restrict__ dx,
@@ -55,18 +57,21 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const bf16* __restrict__ 
                                                        int rows_per_wave) {
   extern __shared__ float sm[];  // [4][2][C]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, C8 = C >> 3;
-  float ag[NP][8], ab[NP][8], gm[NP][8];
+  double ag[NP][8];
+  float ab[NP][8], gm[NP][8];
 #pragma unroll
   for (int i = 0; i < NP; ++i)
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      ag[i][j] = ab[i][j] = 0.f;
+      ag[i][j] = 0.0;
+      ab[i][j] = 0.f;
       const int p = lane + 64 * i;
       gm[i][j] = p < C8 ? gamma[p * 8 + j] : 0.f;
     }
   const int64_t r0 = ((int64_t)blockIdx.x * 4 + wave) * rows_per_wave;
   for (int64_t row = r0; row < r0 + rows_per_wave && row < M; ++row) {
     const float mean = mean_rstd[2 * row], rstd = mean_rstd[2 * row + 1];
+    const double mean_d = mean, rstd_d = rstd;
     F8 xh[NP], g[NP];
     float m1 = 0.f, m2 = 0.f;
 #pragma unroll
@@ -80,7 +85,7 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const bf16* __restrict__ 
           g[i].v[j] = dv.v[j] * gm[i][j];
           m1 += g[i].v[j];
           m2 += g[i].v[j] * xh[i].v[j];
-          ag[i][j] += dv.v[j] * xh[i].v[j];
+          ag[i][j] += (double)dv.v[j] * (((double)xv.v[j] - mean_d) * rstd_d);
           ab[i][j] += dv.v[j];
         }
       }
@@ -104,7 +109,7 @@ __global__ void __launch_bounds__(256) k_layernorm_bwd(const bf16* __restrict__ 
     if (p < C8)
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        sm[(wave * 2 + 0) * C + p * 8 + j] = ag[i][j];
+        sm[(wave * 2 + 0) * C + p * 8 + j] = (float)ag[i][j];
         sm[(wave * 2 + 1) * C + p * 8 + j] = ab[i][j];
       }
   }

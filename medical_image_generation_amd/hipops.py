@@ -471,7 +471,9 @@ def gemm_nt(a, b, *, bias=None, res=None, alpha=1.0, out=None, out_f32=False, ac
     for t, what in ((out, "out"), (res, "res")):
         if t is not None and tuple(t.shape[-2:]) != (m, n):
             raise ValueError(f"{what}: expected [.., {m}, {n}], got {tuple(t.shape)}")
-    assert a.dtype == b.dtype == BF16 and (res is None or res.dtype == BF16) and (out.dtype == F32 or not accumulate)
+    assert a.dtype == b.dtype == BF16 and (res is None or res.dtype == BF16)
+    if accumulate and out.dtype != F32:
+        raise ValueError(f"accumulate adds into an fp32 out, got {out.dtype}")
     sa, sb = _strided(a, batch, "a", vec16=True), _strided(b, batch, "b", vec16=True)
     so, sr = _strided(out, batch, "out", broadcast=False), _strided(res, batch, "res")
     call("mi_gemm_nt_bf16", ptr(a), *sa, ptr(b), *sb, ptr(out), *so, ptr(bias), ptr(res), *sr, m, n, k, *_z(batch), float(alpha),
@@ -481,7 +483,9 @@ def gemm_nt(a, b, *, bias=None, res=None, alpha=1.0, out=None, out_f32=False, ac
 
 def transpose(x, pad_to=None, out=None):
     """[.., R, C] bf16 view -> dense [.., C, P] with the source's row axis last.  P = R, or with pad_to=8 R rounded up to a multiple of 8 (the
-    pitch of a GEMM reduction axis): the kernel zero-fills columns R..P.  out: write into this [.., C, P] view instead."""
+    pitch of a GEMM reduction axis): the kernel zero-fills columns R..P.  out: write into this [.., C, P] view instead.  The kernel
+    zero-fills up to the next multiple of 8 that fits the row pitch whatever pad_to says, so without pad_to a ragged R (R % 8 != 0) is
+    taken only into rows of pitch R: in a wider buffer those zeros would land in columns the view does not own."""
     assert pad_to in (None, 8), "the kernel zero-fills up to the next multiple of 8 only"
     r, c = x.shape[-2:]
     p = (r + 7) // 8 * 8 if pad_to else r
@@ -491,6 +495,10 @@ def transpose(x, pad_to=None, out=None):
     if tuple(out.shape[-2:]) != (c, p) or x.dtype != BF16 or out.dtype != BF16:
         raise ValueError(f"out: expected bf16 [.., {c}, {p}], got {out.dtype} {tuple(out.shape)}")
     sx, so = _strided(x, batch, "x"), _strided(out, batch, "out", broadcast=False)
+    if p % 8 and so[0] != p:
+        p8 = (p + 7) // 8 * 8
+        raise ValueError(f"out: row pitch {so[0]} with {p} columns, not a multiple of 8: the kernel's zero fill of columns "
+                         f"{p}..{min(p8, so[0])} would leave the view (pass pad_to=8 and a [.., {c}, {p8}] view)")
     call("mi_transpose_bf16", ptr(x), *sx, ptr(out), *so, r, c, *_z(batch))
     return out
 

@@ -44,6 +44,8 @@ def test_gemm_nt_refuses_what_the_kernel_cannot_take(no_call):
         hipops.gemm_nt(_bf(5, 20)[:, :16], _bf(7, 16))                      # 40-byte row pitch
     with pytest.raises(ValueError, match=r"expected \[.., 5, 7\]"):
         hipops.gemm_nt(a, b, res=_bf(2, 3, 5, 8))
+    with pytest.raises(ValueError, match="accumulate adds into an fp32 out"):
+        hipops.gemm_nt(a, b, out=_bf(2, 3, 5, 7), accumulate=True)
 
 
 def test_transpose_refuses_what_the_kernel_cannot_take(no_call):
@@ -57,6 +59,30 @@ def test_transpose_refuses_what_the_kernel_cannot_take(no_call):
         hipops.transpose(_bf(2, 3, 5, 16), pad_to=8, out=_bf(2, 3, 16, 5))
     with pytest.raises(AssertionError):
         hipops.transpose(_bf(5, 16), pad_to=16)
+    # k_transpose zero-fills columns R .. min(R rounded up to 8, pitch): with R % 8 != 0 and a wider pitch they are a neighbour's
+    for out in (_bf(16, 40)[:, :5], _bf(16, 8)[:, :5], _bf(2, 3, 16, 6)[..., :5], _bf(1, 40)[:, :5]):
+        with pytest.raises(ValueError, match="row pitch"):
+            hipops.transpose(_bf(*out.shape[:-2], 5, out.shape[-2]), out=out)
+    with pytest.raises(ValueError, match="row pitch"):
+        hipops.transpose(_bf(13, 16), out=_bf(16, 15)[:, 2:])                # the first 2 columns of the NEXT row would be zeroed
+
+
+def test_transpose_takes_every_view_its_zero_fill_stays_inside(monkeypatch):
+    """... and nothing else is refused: a dense ragged output (pitch R), a wider pitch with R % 8 == 0, and any pitch with pad_to=8."""
+    calls = []
+    monkeypatch.setattr(hipops, "call", lambda name, *args: calls.append((name,) + args))
+    monkeypatch.setattr(hipops, "ptr", lambda t: None if t is None else t.data_ptr())
+    hipops.transpose(_bf(5, 16))
+    assert calls.pop()[5:9] == (_ANY, 5, 0, 0)
+    hipops.transpose(_bf(2, 5, 16), out=_bf(2, 16, 5))
+    assert calls.pop()[6:8] == (5, 80)
+    hipops.transpose(_bf(8, 16), out=_bf(16, 40)[:, 32:])
+    assert calls.pop()[6] == 40
+    hipops.transpose(_bf(5, 16), pad_to=8, out=_bf(16, 40)[:, :8])
+    assert calls.pop()[6] == 40
+    hipops.transpose(_bf(2, 3, 27, 16), pad_to=8, out=_bf(2, 3, 16, 64)[..., 32:])
+    assert calls.pop()[6:11] == (64, 3 * 16 * 64, 16 * 64, 27, 16)
+    assert not calls
 
 
 def test_views_reach_the_library_with_their_own_strides(monkeypatch):
