@@ -41,7 +41,8 @@ int mi_copy_channels(const void* src, int Cs, int c0s, void* dst, int Cd, int c0
 /* ---- aten::upsample_nearest3d (+backward): F.interpolate(mode="nearest"), UNet:580, AEKL:99 ----------------------------- */
 int mi_upsample_nearest_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t stream);
 int mi_upsample_nearest_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t stream);
-/* space<->depth rearrangement used by strided convolutions; (D,H,W,C) always describe the SPACE-side tensor */
+/* space<->depth rearrangement used by strided convolutions; (D,H,W,C) always describe the SPACE-side tensor.
+ * These four refuse null pointers, non-positive N / dims / C, C % 8 != 0 and factors below 1 (MI_ERR_BAD_ARG). */
 int mi_space_to_depth(const void* in, int in_cstride, void* out, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t stream);
 int mi_depth_to_space(const void* in, void* out, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t stream);
 
@@ -200,7 +201,8 @@ int mi_linear_wgrad_bf16(const void* x, int ldx, int in_features, const void* dy
                          float* dbias, hipStream_t stream);
 
 int mi_colsum_bf16(const void* x, float* out, int out_stride, int N, int64_t V, int C, int accumulate, hipStream_t stream);
-/* tiny fp32 helpers for bias / embedding vectors: y[r][c] += x[r][c];  out[c] (+)= sum_r in[r][c] */
+/* tiny fp32 helpers for bias / embedding vectors: y[r][c] += x[r][c];  out[c] (+)= sum_r in[r][c].  Row pitches are >= cols
+ * (MI_ERR_BAD_ARG otherwise); ldx = 0 adds the one row x to every row of y. */
 int mi_add_f32_2d(const float* x, int ldx, float* y, int ldy, int rows, int cols, hipStream_t stream);
 int mi_sum_rows_f32(const float* in, int ld, int rows, int cols, float* out, int accumulate, hipStream_t stream);
 int mi_zero_f32_2d(float* x, int ld, int rows, int cols, hipStream_t stream);

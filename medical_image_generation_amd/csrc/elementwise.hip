@@ -660,22 +660,23 @@ int mi_copy_channels(const void* src, int Cs, int c0s, void* dst, int Cd, int c0
   return 0;
 }
 int mi_upsample_nearest_fwd(const void* x, void* y, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t st) {
-  if (C & 7 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
+  if (!x || !y || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || C & 7 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
   int64_t total = (int64_t)N * D * fd * H * fh * W * fw * (C / 8);
   hipLaunchKernelGGL(k_upsample_fwd, dim3(grid_for(total)), dim3(kThreads), 0, st, (const bf16*)x, (bf16*)y, D, H, W, C / 8, fd, fh, fw, total);
   MI_CHECK_LAUNCH();
   return 0;
 }
 int mi_upsample_nearest_bwd(const void* dy, void* dx, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t st) {
-  if (C & 7 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
+  if (!dy || !dx || N <= 0 || D <= 0 || H <= 0 || W <= 0 || C <= 0 || C & 7 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
   int64_t total = (int64_t)N * D * H * W * (C / 8);
   hipLaunchKernelGGL(k_upsample_bwd, dim3(grid_for(total)), dim3(kThreads), 0, st, (const bf16*)dy, (bf16*)dx, D, H, W, C / 8, fd, fh, fw, total);
   MI_CHECK_LAUNCH();
   return 0;
 }
 int mi_space_to_depth(const void* in, int in_cs, void* out, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t st) {
+  if (!in || !out || N <= 0 || D <= 0 || H <= 0 || W <= 0 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
   if (in_cs < C || (in_cs & 7)) return MI_ERR_BAD_ARG;
-  if (C & 7) return MI_ERR_BAD_ARG;
+  if (C <= 0 || C & 7) return MI_ERR_BAD_ARG;
   int Dp = (D + fd - 1) / fd, Hp = (H + fh - 1) / fh, Wp = (W + fw - 1) / fw;
   int64_t total = (int64_t)N * Dp * Hp * Wp * fd * fh * fw * (C / 8);
   hipLaunchKernelGGL(k_space_depth, dim3(grid_for(total)), dim3(kThreads), 0, st, (const bf16*)in, (bf16*)out, D, H, W, C / 8, fd, fh, fw, Dp, Hp, Wp, 1, total, in_cs / 8);
@@ -684,7 +685,8 @@ int mi_space_to_depth(const void* in, int in_cs, void* out, int N, int D, int H,
 }
 int mi_depth_to_space(const void* in, void* out, int N, int D, int H, int W, int C, int fd, int fh, int fw, hipStream_t st) {
   // (D, H, W, C) describe the SPACE-side tensor `out`; `in` is [N, ceil(D/fd), ceil(H/fh), ceil(W/fw), fd*fh*fw*C]
-  if (C & 7) return MI_ERR_BAD_ARG;
+  if (!in || !out || N <= 0 || D <= 0 || H <= 0 || W <= 0 || fd < 1 || fh < 1 || fw < 1) return MI_ERR_BAD_ARG;
+  if (C <= 0 || C & 7) return MI_ERR_BAD_ARG;
   int Dp = (D + fd - 1) / fd, Hp = (H + fh - 1) / fh, Wp = (W + fw - 1) / fw;
   int64_t total = (int64_t)N * Dp * Hp * Wp * fd * fh * fw * (C / 8);
   hipLaunchKernelGGL(k_space_depth, dim3(grid_for(total)), dim3(kThreads), 0, st, (const bf16*)in, (bf16*)out, D, H, W, C / 8, fd, fh, fw, Dp, Hp, Wp, 0, total, C / 8);
@@ -881,11 +883,13 @@ int mi_timestep_embedding(const int64_t* t, float* out, int B, int dim, float ma
   return 0;
 }
 int mi_silu_f32(const float* x, float* y, int64_t n, hipStream_t st) {
+  if (n <= 0 || !x || !y) return MI_ERR_BAD_ARG;  // n = 0 would launch an empty grid
   hipLaunchKernelGGL(k_silu_f32, dim3(ceil_div(n, 256)), dim3(256), 0, st, x, y, n);
   MI_CHECK_LAUNCH();
   return 0;
 }
 int mi_silu_bwd_f32(const float* x, const float* dy, float* dx, int64_t n, hipStream_t st) {
+  if (n <= 0 || !x || !dy || !dx) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_silu_bwd_f32, dim3(ceil_div(n, 256)), dim3(256), 0, st, x, dy, dx, n);
   MI_CHECK_LAUNCH();
   return 0;
@@ -928,7 +932,8 @@ int mi_logvar_to_sigma_bwd(const void* dsigma, const void* logvar, const void* s
   return 0;
 }
 int mi_add_f32_2d(const float* x, int ldx, float* y, int ldy, int rows, int cols, hipStream_t st) {
-  if (rows <= 0 || cols <= 0) return MI_ERR_BAD_ARG;
+  if (rows <= 0 || cols <= 0 || !x || !y) return MI_ERR_BAD_ARG;
+  if (ldy < cols || (ldx != 0 && ldx < cols)) return MI_ERR_BAD_ARG;  // ldx = 0 broadcasts one row; any other pitch below cols overlaps rows
   hipLaunchKernelGGL(k_add_f32_2d, dim3(ceil_div((int64_t)rows * cols, 256)), dim3(256), 0, st, x, ldx, y, ldy, rows, cols);
   MI_CHECK_LAUNCH();
   return 0;
@@ -939,7 +944,7 @@ int mi_zero_f32_2d(float* x, int ld, int rows, int cols, hipStream_t st) {
   return (int)e;
 }
 int mi_sum_rows_f32(const float* in, int ld, int rows, int cols, float* out, int accumulate, hipStream_t st) {
-  if (rows <= 0 || cols <= 0) return MI_ERR_BAD_ARG;
+  if (rows <= 0 || cols <= 0 || !in || !out || ld < cols) return MI_ERR_BAD_ARG;
   hipLaunchKernelGGL(k_sum_rows_f32, dim3(ceil_div(cols, 256)), dim3(256), 0, st, in, ld, rows, cols, out, accumulate);
   MI_CHECK_LAUNCH();
   return 0;
