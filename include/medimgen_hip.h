@@ -529,6 +529,37 @@ int mi_mse_eval(const void* pred, const float* target, double* acc, int N, int C
 int mi_l1_eval(const void* pred, const float* target, double* acc, int N, int C, int64_t V, hipStream_t stream);
 int mi_kl_eval(const void* mu, const void* sigma, double* acc, int N, int C, int64_t V, hipStream_t stream);
 
+/* ---- case preprocessing (configuration.py: resample_image_label 1105-1167, crop_image_label 1048-1071,
+ * normalize_zscore_then_minmax 1204-1221, process_patient 1383-1430; the older form preprocess_dataset.py:21-51): raw array in,
+ * training case out, fp32 buffers on the device.  The reference resamples with scipy.ndimage.zoom one axis at a time
+ * (configuration.py:1126-1129, defaults mode="constant", prefilter=True, grid_mode=False); an axis pass sees the volume as a
+ * contiguous [A][n][B] view.
+ *   mi_pp_prefilter3: c = cubic B-spline coefficients of x along n (gain 6, pole sqrt(3) - 2, whole-sample mirror), out of place
+ *     (x != c), n >= 2.  init_w[n_init] (device, n_init <= min(n, 64)): weights of the causal start c[0] = 6 sum_k init_w[k] x[k] --
+ *     the exact mirror sum when n_init == n, its truncation otherwise (the caller decides; |z|^k < 1e-18 from k = 32).
+ *   mi_pp_resample_axis: dst[a][o][b] = sum_{k < ntaps} tap_w[o][k] * src[a][tap_idx[o][k]][b]; tap tables are [n_out][4] (device),
+ *     ntaps 1 (order 0: the value is copied, weights unread), 2 (order 1) or 4 (order 3, src = the prefiltered coefficients);
+ *     every index must lie in [0, n) -- the caller resolves mirroring and clamping.
+ *   mi_pp_resample_labels (configuration.py:1133-1155 without the one-hot volumes): label fp32 [X][Y][Z] -> out uint8 [Xo][Yo][Zo];
+ *     per output voxel the score of values[v] (device, ascending, nvalues <= 32, each an integer in [0, 255]) is the separable
+ *     two-tap sum of the indicator label == values[v] (tables [n_out][2] per axis; order 0 or an untouched axis: weights {1, 0});
+ *     argmax, ties to the lowest v, also when every score is 0. */
+int mi_pp_prefilter3(const float* x, float* c, int64_t A, int n, int64_t B, const float* init_w, int n_init, hipStream_t stream);
+int mi_pp_resample_axis(const float* src, float* dst, int64_t A, int n, int n_out, int64_t B, const int* tap_idx, const float* tap_w, int ntaps, hipStream_t stream);
+int mi_pp_resample_labels(const float* label, uint8_t* out, const float* values, int nvalues, int X, int Y, int Z, int Xo, int Yo, int Zo, const int* ix, const float* wx, const int* iy, const float* wy, const int* iz, const float* wz, hipStream_t stream);
+/* crop_image_label (configuration.py:1052-1055): box[6] (device ints) = min x, y, z and max x, y, z of x != 0 over all channels of
+ * x [X][Y][Z][C]; {INT_MAX x 3, -1 x 3} when everything is zero. */
+int mi_pp_nonzero_box(const float* x, int X, int Y, int Z, int C, int* box, hipStream_t stream);
+/* per channel inside the box [x0, x0 + nx) x [y0, y0 + ny) x [z0, z0 + nz): stats[C][4] (device doubles) = sum, sum of squares,
+ * min, max; partials folded in a fixed order in fp64.  workspace: mi_pp_stats_workspace_bytes(C) bytes, 8-byte aligned. */
+int64_t mi_pp_stats_workspace_bytes(int C);
+int mi_pp_box_stats(const float* x, int X, int Y, int Z, int C, int x0, int y0, int z0, int nx, int ny, int nz, double* stats, double* workspace, hipStream_t stream);
+/* process_patient's crop, transpose (configuration.py:1395-1399) and normalize_zscore_then_minmax in one pass:
+ * out[c][z][y][x] = (x[x0 + x][y0 + y][z0 + z][c] - lo_inv[c][0]) * lo_inv[c][1] (lo_inv device fp32 [C][2] = min, 1 / (max - min):
+ * the z-score's mean and deviation cancel in (z - z_min) / (z_max - z_min)).  The label gets the crop and the transpose. */
+int mi_pp_finish_image(const float* x, float* out, int X, int Y, int Z, int C, int x0, int y0, int z0, int nx, int ny, int nz, const float* lo_inv, hipStream_t stream);
+int mi_pp_finish_label(const uint8_t* label, uint8_t* out, int X, int Y, int Z, int x0, int y0, int z0, int nx, int ny, int nz, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -140,9 +140,18 @@ _SIGS = {
     "mi_mse_eval": [_p, _p, _p, _i, _i, _l, _p],
     "mi_l1_eval": [_p, _p, _p, _i, _i, _l, _p],
     "mi_kl_eval": [_p, _p, _p, _i, _i, _l, _p],
+    "mi_pp_prefilter3": [_p, _p, _l, _i, _l, _p, _i, _p],
+    "mi_pp_resample_axis": [_p, _p, _l, _i, _i, _l, _p, _p, _i, _p],
+    "mi_pp_resample_labels": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
+    "mi_pp_nonzero_box": [_p, _i, _i, _i, _i, _p, _p],
+    "mi_pp_stats_workspace_bytes": [_i],
+    "mi_pp_box_stats": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
+    "mi_pp_finish_image": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
+    "mi_pp_finish_label": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
 }
-_RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l}
-_NOCHECK = {"mi_abi_version", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_conv1x1_skip_fusable", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
+_RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l,
+        "mi_pp_stats_workspace_bytes": _l}
+_NOCHECK = {"mi_abi_version", "mi_pp_stats_workspace_bytes", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_conv1x1_skip_fusable", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
             "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits"}
 
 _lib = None

@@ -85,6 +85,14 @@ class ResidentDataset:
         image, properties = load_image(data_path, name)
         self.add(name, np.asarray(image), properties.get("class_locations"))
 
+    def add_raw(self, name, image, spacing, target_spacing, label=None, **kw):
+        """One RAW case: image (x, y, z[, c]) at voxel `spacing`, resampled to `target_spacing`, cropped, transposed and normalised on
+        the device (preprocess.preprocess_case, the reference's process_patient) and added.  Returns preprocess_case's result."""
+        from .preprocess import preprocess_case
+        result = preprocess_case(image, spacing, target_spacing, label=label, **kw)
+        self.add(name, result["image"], result["properties"]["class_locations"])
+        return result
+
     def __len__(self):
         return len(self.ids)
 
