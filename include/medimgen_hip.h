@@ -420,49 +420,36 @@ int mi_qsample_drop(const float* x0, const float* noise, const float* sqrt_alpha
 int mi_select_labels(const int64_t* labels, const uint8_t* drop, int64_t null_class, int64_t* out, int B, hipStream_t stream);
 /* dst (bf16 [N][row]) = src (fp32 [N][row]) with the rows of dropped samples zero: the cross-attention context, row = tokens * dim */
 int mi_cast_bf16_drop(const float* src, void* dst, const uint8_t* drop, int N, int64_t row, hipStream_t stream);
-/* one reverse step of DDPMScheduler.step (third-party `generative`; epsilon prediction, "fixed_small" variance) as the inferers'
- * sample loops call it (train_ldm.py:349-365, train_ddpm.py:238-246): x (fp32 NCDHW) is updated in place and also written as the
- * next model input x_cl (NDHWC bf16, may be NULL); eps = model output (NDHWC bf16); noise fp32 NCDHW;
- * coef: [T][5] = 1/sqrt(acp_t), sqrt(1-acp_t), c_x0, c_xt, sigma_t (0 at t = 0); t: device pointer to the (single) timestep;
- * clip: bit 0 = clip_sample (predicted x0 clamped to [-1, 1]), bit 1 = the model output is the velocity (v-prediction) */
-int mi_ddpm_step(float* x, const void* eps, const float* noise, const float* coef, const int64_t* t, void* x_cl, int x_cl_cs, int N,
-                 int C, int64_t V, int clip, hipStream_t stream);
-/* (x_cl_cs >= C: voxel pitch of x_cl in elements -- with mode="concat" sampling the model input holds the condition channels behind
- * the C sample channels and only the sample channels are rewritten per step) */
-/* one step of DDIMScheduler.step / reversed_step (third-party `generative`; Song et al. 2021 as upstream implements it, restated in
- * tests/ddim_ref.py: PARITY UNPINNED -- the reference holds no vectors for it), the few-step scheduler that passes to the same
- * `inferer.sample(..., scheduler=...)` call (train_ldm.py:351-364).  Layouts as above: x fp32 NCDHW updated in place, model_out NDHWC
- * bf16, noise fp32 NCDHW (read only where r4 != 0), x_cl optional NDHWC bf16 with voxel pitch x_cl_cs >= C (channels behind the first
- * C are not touched).  rows: [S][5] fp32 on the device, built by the host per direction, stride and eta =
- * sqrt(a_t), sqrt(1-a_t), sqrt(a_prev), sqrt(1-a_prev-sigma^2), sigma;  row_index: device pointer to the row of this step.
+/* THE update launch of the inferers' sample loops (train_ldm.py:349-365, train_ddpm.py:238-246): one step of either scheduler, plain,
+ * under classifier-free guidance, composited with a known image, or both.  x (fp32 NCDHW, batch N) is updated in place and also
+ * written as the next model input x_cl (NDHWC bf16, may be NULL; x_cl_cs >= C is its voxel pitch in elements -- with mode="concat"
+ * sampling the condition channels sit behind the C sample channels and only the sample channels are rewritten per step);
+ * model_out: the model output (NDHWC bf16); noise: fp32 NCDHW, read only where its factor in the row is non-zero;
+ * index: device pointer to the (single) row of table this step reads; flags: bit 0 = clip_sample (predicted x0 clamped to [-1, 1]),
+ * bit 1 = the model output is the velocity (v-prediction).
+ * ddim = 0 -- DDPMScheduler.step (third-party `generative`; "fixed_small" variance; restated in oracle/step.py: PARITY UNPINNED):
+ *   table: [T][5] = 1/sqrt(acp_t), sqrt(1-acp_t), c_x0, c_xt, sigma_t (0 at t = 0); index = t.
+ * ddim != 0 -- DDIMScheduler.step / reversed_step (third-party `generative`; Song et al. 2021 as upstream implements it, restated in
+ *   tests/ddim_ref.py: PARITY UNPINNED), the few-step scheduler of the same `inferer.sample(..., scheduler=...)` call
+ *   (train_ldm.py:351-364).  table: rows [S][5] the host builds per direction, stride and eta = sqrt(a_t), sqrt(1-a_t), sqrt(a_prev),
+ *   sqrt(1-a_prev-sigma^2), sigma; index = the row of this step.
  *   epsilon: x0 = (x - r1 m) / r0, e = m;   v-prediction: x0 = r0 x - r1 m, e = r0 m + r1 x;   x_next = r2 clip(x0) + r3 e + r4 z
- * flags: bit 0 = clip_sample, bit 1 = v-prediction (as the clip argument above) */
-int mi_ddim_step(float* x, const void* model_out, const float* noise, const float* rows, const int64_t* row_index, void* x_cl,
-                 int x_cl_cs, int N, int C, int64_t V, int flags, hipStream_t stream);
-/* the two steps above under classifier-free guidance (not part of the reference: PARITY UNPINNED).  model_out: NDHWC bf16 of batch 2N
- * from ONE forward -- rows [0, N) with the condition, rows [N, 2N) with the null condition (zero context / condition channels, the
- * null class); guidance: device pointer to the scale w (one captured graph serves every scale).  The kernel forms
- *   m = m_uncond + w (m_cond - m_uncond)   in fp32
- * and continues with exactly the arithmetic of the unguided entry (same table row, same clip / v-prediction bits, noise read only
- * where its factor is non-zero).  x: fp32 NCDHW of batch N, updated in place; x_cl (optional): NDHWC bf16 of batch 2N with voxel pitch
- * x_cl_cs >= C -- the bf16 copy of the new sample goes into the first C channels of BOTH halves, the channels behind them stay */
-int mi_ddpm_step_guided(float* x, const void* model_out, const float* noise, const float* coef, const int64_t* t, const float* guidance,
-                        void* x_cl, int x_cl_cs, int N, int C, int64_t V, int clip, hipStream_t stream);
-int mi_ddim_step_guided(float* x, const void* model_out, const float* noise, const float* rows, const int64_t* row_index,
-                        const float* guidance, void* x_cl, int x_cl_cs, int N, int C, int64_t V, int flags, hipStream_t stream);
-/* one step of image-conditioned sampling: masked inpainting in the manner of RePaint (Lugmayr et al. 2022; not part of the reference:
- * PARITY UNPINNED), composited inside the update launch.  The arguments of mi_ddim_step_guided -- guidance may be NULL: unguided,
- * model_out of batch N, x_cl of batch N -- with ddim selecting the scheduler (0: table = the [T][5] coefficients of mi_ddpm_step and
- * index = t; else the DDIM rows and the row index), and
+ * guidance (NULL: unguided, model_out and x_cl of batch N) -- classifier-free guidance (not part of the reference: PARITY UNPINNED):
+ *   device pointer to the scale w (one captured graph serves every scale); model_out is of batch 2N from ONE forward -- rows [0, N)
+ *   with the condition, rows [N, 2N) with the null condition (zero context / condition channels, the null class).  The kernel forms
+ *   m = m_uncond + w (m_cond - m_uncond) in fp32 and continues with exactly the unguided arithmetic; x_cl is of batch 2N, and the
+ *   bf16 copy of the new sample goes into the first C channels of BOTH halves.
+ * mask, image, known_noise, known (all four NULL: the plain step; all four set: composited; anything else is refused) -- masked
+ *   inpainting in the manner of RePaint (Lugmayr et al. 2022; not part of the reference: PARITY UNPINNED), inside the update launch.
  *   mask: fp32 [N][V], one value per voxel for every channel;  image, known_noise: fp32 NCDHW, the known content and its noise;
  *   known: [rows][4] fp32, indexed by the same device scalar as table = sqrt(A_next), sqrt(1 - A_next), sqrt(A_t / A_next),
  *   sqrt(1 - A_t / A_next), A_next the level the step arrives at (the last two are the host's, for mi_renoise).
- * Per element, m = mask[n][v]:   m >= 1: the value of the entries above (image and known_noise are not read);
+ *   Per element, m = mask[n][v]:   m >= 1: the value of the plain step (image and known_noise are not read);
  *   m <= 0: known[0] image + known[1] known_noise (model_out, x and noise are not read);   else m x_gen + (1 - m) x_known.
- * Mask-1 voxels carry the bits of the entries above; a NaN in a buffer that is not read does not reach x or x_cl */
-int mi_step_inpaint(float* x, const void* model_out, const float* noise, const float* table, const int64_t* index, const float* guidance,
-                    const float* mask, const float* image, const float* known_noise, const float* known, void* x_cl, int x_cl_cs, int N,
-                    int C, int64_t V, int flags, int ddim, hipStream_t stream);
+ *   A selection, not a lerp: mask-1 voxels carry the bits of the plain step; a NaN in a buffer that is not read does not reach x or x_cl */
+int mi_diffusion_step(float* x, const void* model_out, const float* noise, const float* table, const int64_t* index, const float* guidance,
+                      const float* mask, const float* image, const float* known_noise, const float* known, void* x_cl, int x_cl_cs, int N,
+                      int C, int64_t V, int flags, int ddim, hipStream_t stream);
 /* one forward-diffusion move (resampling between two steps of the entry above): x = a x + b noise in place, fp32 NCDHW; the bf16 copy
  * goes into the first C channels of `halves` (1, or 2 for a guided loop) batches of x_cl (optional, NDHWC, voxel pitch x_cl_cs >= C) */
 int mi_renoise(float* x, const float* noise, float a, float b, void* x_cl, int x_cl_cs, int N, int halves, int C, int64_t V,

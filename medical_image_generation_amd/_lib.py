@@ -115,11 +115,7 @@ _SIGS = {
     "mi_ls_gan_loss": [_p, _i, _l, _f, _f, _p, _p, _f, _p],
     "mi_bn_running_update": [_p, _p, _p, _p, _i, _f, _f, _l, _p],
     "mi_qsample": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p],
-    "mi_ddpm_step": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
-    "mi_ddim_step": [_p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
-    "mi_ddpm_step_guided": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
-    "mi_ddim_step_guided": [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _p],
-    "mi_step_inpaint": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, _p],
+    "mi_diffusion_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, _p],
     "mi_renoise": [_p, _p, _f, _f, _p, _i, _i, _i, _i, _l, _p],
     "mi_qsample_drop": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p, _p],
     "mi_select_labels": [_p, _p, _l, _p, _i, _p],
@@ -158,7 +154,7 @@ _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
 # lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
 # an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 
 def exported_symbols() -> list[str]:

@@ -1,3 +1,3 @@
 #include "common.h"
 #include "medimgen_hip.h"
-extern "C" int mi_abi_version(void) { return 19; }
+extern "C" int mi_abi_version(void) { return 20; }

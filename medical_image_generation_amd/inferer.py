@@ -7,29 +7,33 @@ sites use (same names, argument meaning, return values).  The scheduler arithmet
 implements it, restated in oracle/step.py (`DDPMSchedule.step`): PARITY UNPINNED -- the reference holds no vectors for it; the
 tests pin the kernel against that restatement.
 
-One denoising step = UNet forward (no tape) + ONE fused update kernel (`mi_ddpm_step`: predicted x0, clip, posterior mean, noise;
-it also writes the next step's channels-last bf16 model input), captured once as a hipGraph and replayed per timestep -- the
-timestep is a device scalar the embedding and update kernels read, so all 1000 steps share one graph.
+One denoising step = UNet forward (no tape) + ONE fused update launch (`mi_diffusion_step`: predicted x0, clip, the scheduler's update,
+noise; it also writes the next step's channels-last bf16 model input), captured once as a hipGraph and replayed per timestep -- the
+timestep is a device scalar the embedding and update kernels read, so all 1000 steps share one graph.  Every loop below makes that
+one call, with NULL for what it was not built with (guidance scale, known region).
 
 Few-step sampling and image-to-noise inversion go through `DDIMScheduler` (third-party `generative` as well, Song et al. 2021 as
-upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED): the same loop with `mi_ddim_step` as the update kernel,
-which reads row i of a per-run table of step constants, so step count, eta and direction change without a new capture.
+upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED): the same loop and launch with `ddim` set, which reads row i
+of a per-run table of step constants, so step count, eta and direction change without a new capture.  The scheduler kind reaches the
+loop in that argument alone; the rest it asks of the `_Scheduler` interface.
 
 Class-conditional models sample with `class_labels=`.  Classifier-free guidance (`guidance_scale=`; Ho & Salimans 2022 -- not part of the
-reference; PARITY UNPINNED): every step is ONE forward at batch 2N -- the conditional half [0, N) and the null half [N, 2N) -- and one
-`mi_ddpm_step_guided` / `mi_ddim_step_guided` launch that forms m = m_uncond + w (m_cond - m_uncond) and continues with the unguided
-arithmetic.  Null means zeros for the cross-attention context and the concatenated condition channels, and `null_class` for the
-class route -- what trainer.DDPMTrainer(..., null_class=).step(..., drop) trains.  w is a device scalar: one graph serves every scale.
+reference; PARITY UNPINNED): every step is ONE forward at batch 2N -- the conditional half [0, N) and the null half [N, 2N) -- and the
+update launch forms m = m_uncond + w (m_cond - m_uncond) and continues with the unguided arithmetic.  Null means zeros for the
+cross-attention context and the concatenated condition channels, and `null_class` for the class route -- what
+trainer.DDPMTrainer(..., null_class=).step(..., drop) trains.  w is a device scalar: one graph serves every scale.
 
 Image-conditioned sampling (`img2img`, `inpaint`; SDEdit, Meng et al. 2022, and masked inpainting in the manner of RePaint, Lugmayr et al.
 2022 -- not part of the reference; PARITY UNPINNED): a run may start part-way down the step list, from the image noised to that level,
-and with a mask every step is still ONE forward plus ONE launch -- `mi_step_inpaint` composites inside the update: the generated value
-where the mask is 1, the known image at the level the step arrives at where it is 0 (a per-step `known` table beside the step table).
+and with a mask every step is still ONE forward plus ONE launch, which composites inside the update: the generated value where the
+mask is 1, the known image at the level the step arrives at where it is 0 (a per-step `known` table beside the step table).
 Resampling is a list of moves: denoising steps, replayed from the same graph, and forward-diffusion moves (`mi_renoise`) between them.
 Mask, image and known-region noise are buffers, the known rows a table the captured step already points at; the start and the move list
 only choose which replays happen: one captured graph serves every run-time choice.
 """
 from __future__ import annotations
+
+import math
 
 import torch
 
@@ -51,7 +55,7 @@ def betas(schedule, num_train_timesteps, beta_start, beta_end):
 
 def _known_rows(a, a_next):
     """fp32 [len(a), 4] = sqrt(A_next), sqrt(1 - A_next), sqrt(A_t / A_next), sqrt(1 - A_t / A_next) for steps that leave the level a
-    (fp64) and arrive at a_next: the known region at the arrival level is [0] image + [1] noise (`mi_step_inpaint`), and [2] x + [3] noise
+    (fp64) and arrive at a_next: the known region at the arrival level is [0] image + [1] noise (`mi_diffusion_step`), and [2] x + [3] noise
     takes a sample back from a_next to a (`mi_renoise`).  fp64 with every radicand clamped at 0, kept as fp32."""
     q = a / a_next
     return torch.stack([a_next.clamp(min=0).sqrt(), (1 - a_next).clamp(min=0).sqrt(), q.clamp(min=0).sqrt(), (1 - q).clamp(min=0).sqrt()],
@@ -80,42 +84,87 @@ def resample_moves(n_steps, jump_length, jump_n_sample, start=0):
     return moves
 
 
-class DDPMScheduler:
-    """`generative.networks.schedulers.DDPMScheduler` as train_ldm.py:74 constructs it (variance_type "fixed_small")."""
+class _Scheduler:
+    """What both schedulers share: the beta schedule, the checks, add_noise / get_velocity, the per-device tables, and what the fused
+    loop asks of either -- `ddim`, `flags`, [known_]coefficients(), known_rows(), _steps, _fill, _index, _draws (the defaults: DDPM's)."""
+    ddim = 0  # the table form the update kernel reads: 0 = [T][5] coefficients indexed by t, 1 = per-run rows indexed by the step
 
-    def __init__(self, num_train_timesteps=1000, schedule="linear_beta", variance_type="fixed_small", clip_sample=True,
-                 prediction_type="epsilon", beta_start=1e-4, beta_end=2e-2):
-        if variance_type != "fixed_small":
-            raise NotImplementedError("only variance_type='fixed_small' (the upstream default the reference uses)")
+    def __init__(self, num_train_timesteps, schedule, clip_sample, prediction_type, beta_start, beta_end):
         if prediction_type not in ("epsilon", "v_prediction"):
             raise ValueError(f"unknown prediction_type {prediction_type}")
         self.betas = betas(schedule, num_train_timesteps, beta_start, beta_end)
         self.num_train_timesteps, self.prediction_type, self.clip_sample = num_train_timesteps, prediction_type, clip_sample
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._dev = {}
+
+    @property
+    def flags(self):  # of the update kernel: bit 0 = clip_sample, bit 1 = v-prediction
+        return int(self.clip_sample) | (2 if self.prediction_type == "v_prediction" else 0)
+
+    def _stride(self, num_inference_steps):
+        if num_inference_steps > self.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`: "
+                             f"{self.num_train_timesteps}")
+        return self.num_train_timesteps // num_inference_steps
+
+    def _device_table(self, name, device, make):
+        """A device table, allocated once per device (make() -> its host form): a captured graph that points at it stays valid."""
+        table = self._dev.get(name)
+        if table is None or table.device != torch.device(device):
+            table = self._dev[name] = make().to(device)
+        return table
+
+    def _levels(self, like, timesteps):
+        a = self.alphas_cumprod.to(like.device)[timesteps]
+        shape = (-1,) + (1,) * (like.ndim - 1)
+        return (a ** 0.5).reshape(shape), ((1 - a) ** 0.5).reshape(shape)
+
+    def add_noise(self, original_samples, noise, timesteps):
+        sa, sb = self._levels(original_samples, timesteps)
+        return sa * original_samples + sb * noise
+
+    def get_velocity(self, sample, noise, timesteps):
+        sa, sb = self._levels(sample, timesteps)
+        return sa * noise - sb * sample
+
+    def _steps(self, reverse=False):  # the timesteps in the order the loop takes them
+        return [int(t) for t in (self.timesteps.flip(0) if reverse else self.timesteps)]
+
+    def _fill(self, coef, known, known_rows, index, eta, reverse):
+        """This run's rows into the device tables the (possibly captured) step reads; DDPM's hold every timestep: nothing to do."""
+
+    def _index(self, i, t):  # what the update kernel indexes its tables with at step i, timestep t
+        return t
+
+    def _draws(self, t, eta, reverse):  # whether the step at timestep t reads z (sigma != 0)
+        return t > 0
+
+
+class DDPMScheduler(_Scheduler):
+    """`generative.networks.schedulers.DDPMScheduler` as train_ldm.py:74 constructs it (variance_type "fixed_small")."""
+
+    def __init__(self, num_train_timesteps=1000, schedule="linear_beta", variance_type="fixed_small", clip_sample=True,
+                 prediction_type="epsilon", beta_start=1e-4, beta_end=2e-2):
+        if variance_type != "fixed_small":
+            raise NotImplementedError("only variance_type='fixed_small' (the upstream default the reference uses)")
+        super().__init__(num_train_timesteps, schedule, clip_sample, prediction_type, beta_start, beta_end)
         acp, b = self.alphas_cumprod.double(), self.betas.double()
         prev = torch.cat([torch.ones(1, dtype=torch.float64), acp[:-1]])
         sigma = ((1 - prev) / (1 - acp) * b).clamp(min=1e-20).sqrt()
         sigma[0] = 0.0  # no noise is added at t = 0
         self._coef = torch.stack([1 / acp.sqrt(), (1 - acp).sqrt(), prev.sqrt() * b / (1 - acp), (1 - b).sqrt() * (1 - prev) / (1 - acp), sigma],
                                  dim=1).float().contiguous()
-        self._coef_dev = self._known_dev = None
         self.set_timesteps(num_train_timesteps)
 
     def set_timesteps(self, num_inference_steps, device=None):
-        if num_inference_steps > self.num_train_timesteps:
-            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`: "
-                             f"{self.num_train_timesteps}")
+        ratio = self._stride(num_inference_steps)
         self.num_inference_steps = num_inference_steps
-        ratio = self.num_train_timesteps // num_inference_steps
-        self.timesteps = (torch.arange(0, num_inference_steps) * ratio).round().flip(0).to(torch.int64)
-        if device is not None:
-            self.timesteps = self.timesteps.to(device)
+        timesteps = (torch.arange(0, num_inference_steps) * ratio).round().flip(0).to(torch.int64)
+        self.timesteps = timesteps if device is None else timesteps.to(device)
 
     def coefficients(self, device):
-        if self._coef_dev is None or self._coef_dev.device != torch.device(device):
-            self._coef_dev = self._coef.to(device)
-        return self._coef_dev
+        return self._device_table("coef", device, lambda: self._coef)
 
     def known_rows(self):
         """fp32 [T, 4], row t: the known-region constants (`_known_rows`) of the step that leaves t -- it arrives at alphas_cumprod[t - 1]
@@ -124,15 +173,8 @@ class DDPMScheduler:
         return _known_rows(acp, torch.cat([torch.ones(1, dtype=torch.float64), acp[:-1]]))
 
     def known_coefficients(self, device):
-        """The device table `mi_step_inpaint` reads beside coefficients(): [num_train_timesteps, 4], one allocation per device."""
-        if self._known_dev is None or self._known_dev.device != torch.device(device):
-            self._known_dev = self.known_rows().to(device)
-        return self._known_dev
-
-    def add_noise(self, original_samples, noise, timesteps):
-        a = self.alphas_cumprod.to(original_samples.device)[timesteps]
-        shape = (-1,) + (1,) * (original_samples.ndim - 1)
-        return (a ** 0.5).reshape(shape) * original_samples + ((1 - a) ** 0.5).reshape(shape) * noise
+        """The device table `mi_diffusion_step` reads beside coefficients(): [num_train_timesteps, 4]."""
+        return self._device_table("known", device, self.known_rows)
 
     def step(self, model_output, timestep, sample, generator=None):
         """(pred_prev_sample, pred_original_sample) for fp32 NC[D]HW tensors -- the upstream signature; the fused loop of the inferers
@@ -151,7 +193,7 @@ class DDPMScheduler:
         return prev, x0
 
 
-class DDIMScheduler:
+class DDIMScheduler(_Scheduler):
     """`generative.networks.schedulers.DDIMScheduler`: the few-step sampler that passes to the same `inferer.sample(..., scheduler=...)`
     call (train_ldm.py:351-364), and `reversed_step`, image-to-noise inversion.  The upstream source is absent; the arithmetic is the
     closed form of Song et al. 2021 as upstream implements it, restated in tests/ddim_ref.py: PARITY UNPINNED -- the reference holds
@@ -164,28 +206,20 @@ class DDIMScheduler:
     every radicand clamped at 0 and kept as fp32; the update for sample x, model output m, noise z:
         epsilon: x0 = (x - r1 m) / r0, e = m;    v_prediction: x0 = r0 x - r1 m, e = r0 m + r1 x
         x_next = r2 clip(x0) + r3 e + r4 z       (e is not recomputed from the clipped x0)"""
+    ddim = 1
 
     def __init__(self, num_train_timesteps=1000, schedule="linear_beta", clip_sample=True, set_alpha_to_one=True, steps_offset=0,
                  prediction_type="epsilon", beta_start=1e-4, beta_end=2e-2):
-        if prediction_type not in ("epsilon", "v_prediction"):
-            raise ValueError(f"unknown prediction_type {prediction_type}")
-        self.betas = betas(schedule, num_train_timesteps, beta_start, beta_end)
-        self.num_train_timesteps, self.prediction_type, self.clip_sample = num_train_timesteps, prediction_type, clip_sample
+        super().__init__(num_train_timesteps, schedule, clip_sample, prediction_type, beta_start, beta_end)
         self.steps_offset = steps_offset
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
         self.final_alpha_cumprod = torch.tensor(1.0) if set_alpha_to_one else self.alphas_cumprod[0]  # the level "before" t = 0
         self.first_alpha_cumprod = torch.tensor(0.0)  # the level "after" t = T - 1 (inversion): pure noise
-        self._table = self._known = None
         # every training timestep, descending; steps_offset shifts the strided subsets of set_timesteps only
         self.num_inference_steps = num_train_timesteps
         self.timesteps = torch.arange(num_train_timesteps - 1, -1, -1, dtype=torch.int64)
 
     def set_timesteps(self, num_inference_steps, device=None):
-        if num_inference_steps > self.num_train_timesteps:
-            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.num_train_timesteps`: "
-                             f"{self.num_train_timesteps}")
-        ratio = self.num_train_timesteps // num_inference_steps
+        ratio = self._stride(num_inference_steps)
         timesteps = (torch.arange(0, num_inference_steps) * ratio).flip(0).to(torch.int64) + self.steps_offset
         if int(timesteps[0]) >= self.num_train_timesteps:
             raise ValueError(f"`steps_offset`: {self.steps_offset} moves the largest of {num_inference_steps} timesteps to "
@@ -214,11 +248,8 @@ class DDIMScheduler:
         return self._rows(self.timesteps.flip(0) if reverse else self.timesteps, eta, reverse).contiguous()
 
     def coefficients(self, device):
-        """The device row table the fused loop reads, [num_train_timesteps, 5]: one allocation per device at full capacity, so a
-        captured graph that points at it stays valid over set_timesteps, eta and direction -- the loop refills it before it steps."""
-        if self._table is None or self._table.device != torch.device(device):
-            self._table = torch.zeros(self.num_train_timesteps, 5, dtype=F32, device=device)
-        return self._table
+        """[num_train_timesteps, 5]: full capacity, valid over set_timesteps, eta and direction -- the loop refills it (`_fill`)."""
+        return self._device_table("coef", device, lambda: torch.zeros(self.num_train_timesteps, 5, dtype=F32))
 
     def known_rows(self, eta=0.0):
         """fp32 [n_steps, 4] in loop order: the known-region constants (`_known_rows`) of the denoising steps, each arriving at the `ap` of
@@ -229,21 +260,21 @@ class DDIMScheduler:
         return _known_rows(acp[t], torch.where(p >= 0, acp[p.clamp(min=0)], self.final_alpha_cumprod.double()))
 
     def known_coefficients(self, device):
-        """The device table `mi_step_inpaint` reads beside coefficients(): [num_train_timesteps, 4], one allocation per device at full
-        capacity, refilled by the loop before it steps -- a captured graph survives set_timesteps."""
-        if self._known is None or self._known.device != torch.device(device):
-            self._known = torch.zeros(self.num_train_timesteps, 4, dtype=F32, device=device)
-        return self._known
+        """The device table `mi_diffusion_step` reads beside coefficients(): [num_train_timesteps, 4], refilled like it."""
+        return self._device_table("known", device, lambda: torch.zeros(self.num_train_timesteps, 4, dtype=F32))
 
-    def add_noise(self, original_samples, noise, timesteps):
-        a = self.alphas_cumprod.to(original_samples.device)[timesteps]
-        shape = (-1,) + (1,) * (original_samples.ndim - 1)
-        return (a ** 0.5).reshape(shape) * original_samples + ((1 - a) ** 0.5).reshape(shape) * noise
+    def _fill(self, coef, known, known_rows, index, eta, reverse):
+        rows = self.rows(eta, reverse)
+        coef[:len(rows)].copy_(rows)
+        index.zero_()  # the warm-up and capture passes read row 0
+        if known is not None:
+            known[:len(known_rows)].copy_(known_rows)
 
-    def get_velocity(self, sample, noise, timesteps):
-        a = self.alphas_cumprod.to(sample.device)[timesteps]
-        shape = (-1,) + (1,) * (sample.ndim - 1)
-        return (a ** 0.5).reshape(shape) * noise - ((1 - a) ** 0.5).reshape(shape) * sample
+    def _index(self, i, t):
+        return i
+
+    def _draws(self, t, eta, reverse):
+        return not (reverse or eta == 0)  # deterministic rows (sigma = 0): the kernel does not read z
 
     def _update(self, r, model_output, sample):
         if self.prediction_type == "v_prediction":
@@ -269,6 +300,30 @@ class DDIMScheduler:
         return self._update(r, model_output, sample)
 
 
+class _Noise:
+    """Where the noise of one run comes from.  z, one per move: noises[j], else drawn from `generator`.  zk, the noise of an inpaint
+    loop's known region: known_noises -- one tensor, or one per "d" move --, else drawn: before every "d" move (fresh), or once, before
+    the first pass.  The loop asks per "d" move for z, then zk: the order of the draws."""
+
+    def __init__(self, noises=None, generator=None, known_noises=None, fresh=False):
+        self.noises, self.generator, self.known_noises = noises, generator, known_noises
+        self.per_move = fresh if known_noises is None else not torch.is_tensor(known_noises)  # zk changes with every "d" move
+
+    def _put(self, buf, pinned):
+        if pinned is not None:
+            buf.copy_(pinned)
+        else:
+            buf.normal_(generator=self.generator)
+
+    def z(self, buf, j):
+        self._put(buf, None if self.noises is None else self.noises[j])
+
+    def zk(self, buf, done=None):
+        """done None: before the first pass, where a once-per-run zk is set; else before "d" move number `done`."""
+        if self.per_move == (done is not None):
+            self._put(buf, self.known_noises[done] if self.per_move and self.known_noises is not None else self.known_noises)
+
+
 class _Loop:
     """One captured denoising step, replayed over scheduler.timesteps."""
 
@@ -276,15 +331,13 @@ class _Loop:
         """cond_channels: channels of a mode="concat" conditioning tensor that sit, un-noised, behind the sample's channels in the model
         input; context_shape: (tokens, cross_attention_dim) of a mode="crossattn" conditioning; labels: the model reads class labels;
         guided: classifier-free guidance -- the model runs at batch 2N (condition, then null condition), the sample stays at batch N;
-        inpaint: the update launch is `mi_step_inpaint` on this loop's image, mask [N, V], known-region noise and known table."""
+        inpaint: the update launch composites with this loop's image, mask [N, V], known-region noise and known table."""
         self.m, self.sch = model, scheduler
         n, c = shape[0], shape[1]
         self.guided = bool(guided)
         nb = 2 * n if self.guided else n  # the model's batch
         sp = tuple(shape[2:])
-        self.v = 1
-        for s in sp:
-            self.v *= s
+        self.v = math.prod(sp)
         dims = (1,) * (3 - len(sp)) + sp
         self.n, self.c = n, c
         self.x = torch.empty(shape, dtype=F32, device=device)                    # the sample, fp32 NC[D]HW
@@ -294,11 +347,11 @@ class _Loop:
         self.labels = torch.zeros(nb, dtype=torch.int64, device=device) if labels else None
         self.w = torch.ones(1, dtype=F32, device=device) if self.guided else None  # the guidance scale the guided update kernel reads
         self.z = torch.empty(shape, dtype=F32, device=device)
-        self.ddim = isinstance(scheduler, DDIMScheduler)
-        self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its table with: t (DDPM), step i (DDIM)
+        self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its tables with (scheduler._index)
         self.tn = torch.zeros(nb, dtype=torch.int64, device=device)  # the timestep the model reads
         self.coef = scheduler.coefficients(device)
         self.inpaint = bool(inpaint)
+        self.image = self.mask = self.zk = self.known = None
         if self.inpaint:
             self.image = torch.zeros(shape, dtype=F32, device=device)       # the known content, at the sample's level of abstraction
             self.mask = torch.ones((n, self.v), dtype=F32, device=device)   # 1: regenerate, 0: keep, between: blend
@@ -312,16 +365,9 @@ class _Loop:
     def _step(self):
         ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
         eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, class_labels=self.labels, context=self.ctx)
-        flags = int(self.sch.clip_sample) | (2 if self.sch.prediction_type == "v_prediction" else 0)
-        if self.inpaint:  # the same step, composited with the known image inside the launch (guidance NULL: unguided)
-            call("mi_step_inpaint", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.w), ptr(self.mask), ptr(self.image),
-                 ptr(self.zk), ptr(self.known), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, flags, int(self.ddim))
-        elif self.guided:  # eps holds both branches: the kernel combines them, steps, and rewrites the sample channels of both halves
-            call("mi_ddim_step_guided" if self.ddim else "mi_ddpm_step_guided", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t),
-                 ptr(self.w), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, flags)
-        else:
-            call("mi_ddim_step" if self.ddim else "mi_ddpm_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.x_cl),
-                 self.c + self.cc, self.n, self.c, self.v, flags)
+        # NULL for what the loop was not built with: w (unguided: eps and x_cl of batch N), the known region (the plain step)
+        call("mi_diffusion_step", ptr(self.x), ptr(eps), ptr(self.z), ptr(self.coef), ptr(self.t), ptr(self.w), ptr(self.mask), ptr(self.image),
+             ptr(self.zk), ptr(self.known), ptr(self.x_cl), self.c + self.cc, self.n, self.c, self.v, self.sch.flags, self.sch.ddim)
 
     def _load(self, x):
         """x (fp32 NC[D]HW) -> the sample channels of the model input (the condition channels behind them stay)."""
@@ -330,20 +376,9 @@ class _Loop:
         for h in range(2 if self.guided else 1):
             self.x_cl[h * self.n:(h + 1) * self.n, ..., :self.c].copy_(x_cl)
 
-    def run(self, input_noise, noises=None, generator=None, use_graph=True, on_step=None, conditioning=None, eta=0.0, reverse=False,
-            class_labels=None, guidance_scale=None, null_class=None, start=0, moves=None, image=None, mask=None, fresh=False,
-            known_noises=None):
-        """eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps.
-        class_labels (int64 [N]), guidance_scale, null_class: what the loop was built for (labels / guided); filled before any step.
-        start: index into the step list of the first step taken (input_noise is then a sample of that step's level); moves: the list
-        `resample_moves` returns, default one "d" per step from `start` -- `noises` holds one z per move, in move order.
-        image, mask ([N, V] fp32): an inpaint loop's known content; fresh: its noise zk is redrawn before every "d" move, else drawn
-        once; known_noises pins it: one tensor, or one per "d" move.  Draw order per "d" move: z, then zk."""
-        if self.m._arena is not self.arena:  # the module moved (.to / .cuda): plans and graph point at the old buffers -> start over
-            self.arena, self.graph, self.keys, self._pinned = self.m.arena(self.x.device), None, (), None
+    def _load_condition(self, conditioning, class_labels, guidance_scale, null_class):
+        """What the loop was built for (concat channels or context, labels, guided), filled before any step."""
         n = self.n
-        if reverse and (self.inpaint or start or moves is not None):
-            raise ValueError("the inversion rows take no mask, start or move list")
         if self.cc:  # mode="concat": model_input = cat([image, conditioning], dim=1) at every step; written once, the steps rewrite `image`
             self.x_cl[:n, ..., self.c:].copy_(ops.to_channels_last(conditioning))
         elif self.ctx is not None:  # mode="crossattn": the context token matrix is a constant of the loop
@@ -358,28 +393,31 @@ class _Loop:
             if self.labels is not None:
                 self.labels[n:].fill_(null_class)
             self.w.fill_(float(guidance_scale))
-        self._load(input_noise)
-        steps = [int(t) for t in self.sch.timesteps]
-        if self.ddim:  # the rows of THIS run, written into the table the (possibly already captured) step reads, before any step runs
-            if reverse:
-                steps.reverse()
-            self.coef[:len(steps)].copy_(self.sch.rows(eta, reverse))
-            self.t.zero_()
+
+    def _load_known(self, image, mask, noise):  # the known region: its content, the mask ([N or 1, 1, *spatial]), a once-per-run zk
+        self.image.copy_(image)
+        self.mask.copy_(mask.to(device=self.x.device, dtype=F32).expand((self.n,) + tuple(mask.shape[1:])).reshape(self.n, -1))
+        noise.zk(self.zk)
+
+    def run(self, x, noise, cond, known=None, use_graph=True, on_step=None, eta=0.0, reverse=False, start=0, moves=None):
+        """x: the sample of step `start` (an index into the step list); noise: a `_Noise`; cond: `_load_condition`'s arguments; known:
+        (image, mask as `inpaint` takes it), an inpaint loop's known content.
+        eta, reverse: DDIM only -- the noise scale of the denoising rows; reverse=True runs the inversion rows over ascending timesteps.
+        moves: the list `resample_moves` returns, default one "d" per step from `start` -- noise.noises holds one z per move."""
+        if self.m._arena is not self.arena:  # the module moved (.to / .cuda): plans and graph point at the old buffers -> start over
+            self.arena, self.graph, self.keys, self._pinned = self.m.arena(self.x.device), None, (), None
+        if reverse and (self.inpaint or start or moves is not None):
+            raise ValueError("the inversion rows take no mask, start or move list")
+        self._load_condition(*cond)
+        self._load(x)
+        steps = self.sch._steps(reverse)
         if moves is None:
             moves = [("d", i) for i in range(start, len(steps))]
-        known = None  # the host's copy of the known rows: mi_renoise takes its two factors by value
-        if self.inpaint or any(kind == "n" for kind, _ in moves):
-            known = self.sch.known_rows(eta) if self.ddim else self.sch.known_rows()
+        # the host's copy of the known rows: mi_renoise takes its two factors by value
+        rows = self.sch.known_rows() if self.inpaint or any(kind == "n" for kind, _ in moves) else None
+        self.sch._fill(self.coef, self.known, rows, self.t, eta, reverse)  # the tables of THIS run, before any step runs
         if self.inpaint:
-            if self.ddim:
-                self.known[:len(steps)].copy_(known)
-            self.image.copy_(image)
-            self.mask.copy_(mask)
-            single = torch.is_tensor(known_noises)
-            if single:
-                self.zk.copy_(known_noises)
-            elif known_noises is None and not fresh:
-                self.zk.normal_(generator=generator)
+            self._load_known(*known, noise)
         keep = self.x.clone()
         if not self.m._plans or len(self.keys) != len(self.m._plans):
             self.keys = ()
@@ -399,31 +437,25 @@ class _Loop:
                 self._step()
             self._pinned = (dict(self.m._plans), dict(ops._ws_cache), self.arena)  # keep what the graph points at alive
         self._load(keep)
+        self._walk(moves, steps, rows, noise, eta, reverse, on_step)
+        return self.x.clone()
+
+    def _walk(self, moves, steps, rows, noise, eta, reverse, on_step):
         done = 0  # "d" moves so far
         for j, (kind, i) in enumerate(moves):
             t = steps[i]
             if kind == "n":  # undo step i: one forward-diffusion move from the level it arrived at, eager, between two replays
-                if noises is not None:
-                    self.z.copy_(noises[j])
-                else:
-                    self.z.normal_(generator=generator)
-                row = known[i if self.ddim else t]
+                noise.z(self.z, j)
+                row = rows[self.sch._index(i, t)]
                 call("mi_renoise", ptr(self.x), ptr(self.z), float(row[2]), float(row[3]), ptr(self.x_cl), self.c + self.cc, self.n,
                      2 if self.guided else 1, self.c, self.v)
                 continue
-            self.t.fill_(i if self.ddim else t)
+            self.t.fill_(self.sch._index(i, t))
             self.tn.fill_(t)
-            if self.ddim and (reverse or eta == 0):
-                pass  # deterministic rows (sigma = 0): the kernel does not read z
-            elif noises is not None:
-                self.z.copy_(noises[j])
-            elif self.ddim or t > 0:
-                self.z.normal_(generator=generator)
-            if self.inpaint and not single:
-                if known_noises is not None:
-                    self.zk.copy_(known_noises[done])
-                elif fresh:
-                    self.zk.normal_(generator=generator)
+            if self.sch._draws(t, eta, reverse):
+                noise.z(self.z, j)
+            if self.inpaint:
+                noise.zk(self.zk, done)
             done += 1
             if self.graph is not None:
                 self.graph.replay()
@@ -431,7 +463,6 @@ class _Loop:
                 self._step()
             if on_step is not None:
                 on_step(i, t, self.x)
-        return self.x.clone()
 
 
 class DiffusionInferer:
@@ -502,6 +533,18 @@ class DiffusionInferer:
                 raise ValueError(f"guidance on a class-conditional model needs null_class= in [0, {nce}): the label of the unconditional branch")
         return conditioning, cc, ctx_shape, class_labels
 
+    def _run(self, image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class, noise, input_noise=None,
+             start=0, mask=None, **how):
+        """The one path from the arguments of sample / img2img / inpaint / invert to the loop and its run.  image: the run's shape and, at
+        start > 0 or under a (checked) mask, its content; noise: a `_Noise`; how: what `_Loop.run` takes besides."""
+        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels,
+                                                                       guidance_scale, null_class)
+        x = self._first_sample(image, input_noise, scheduler, start, noise.generator)
+        known = None if mask is None else (image.float(), mask)
+        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None,
+                          class_labels is not None, mask is not None)
+        return loop.run(x, noise, (conditioning, class_labels, guidance_scale, null_class), known, start=start, **how)
+
     @torch.no_grad()
     def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
                mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
@@ -515,19 +558,14 @@ class DiffusionInferer:
         every step is m_uncond + w (m_cond - m_uncond), from one forward at batch 2N whose second half carries the null condition --
         zero context tokens, zero condition channels, and `null_class` (required with class_labels) as the label.  w = 1 is the
         conditional model, w = 0 the unconditional one; the scale is a device scalar, so all scales share one captured graph."""
-        conditioning, cc, ctx_shape, class_labels = self._conditioning(input_noise, diffusion_model, conditioning, mode, class_labels,
-                                                                       guidance_scale, null_class)
-        scheduler = scheduler or self.scheduler
         inter = []
 
         def on_step(i, t, x):
             if save_intermediates and t % intermediate_steps == 0:
                 inter.append(x.clone())
 
-        loop = self._loop(diffusion_model, scheduler, input_noise.shape, input_noise.device, cc, ctx_shape, guidance_scale is not None,
-                          class_labels is not None)
-        image = loop.run(input_noise.float(), noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning,
-                         eta=eta, class_labels=class_labels, guidance_scale=guidance_scale, null_class=null_class)
+        image = self._run(input_noise, diffusion_model, scheduler or self.scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
+                          _Noise(noises, generator), input_noise, use_graph=use_graph, on_step=on_step, eta=eta)
         return (image, inter) if save_intermediates else image
 
     @staticmethod
@@ -557,6 +595,11 @@ class DiffusionInferer:
         if mask.dim() != len(shape) or mask.shape[1] != 1 or mask.shape[0] not in (1, shape[0]) or tuple(mask.shape[2:]) != tuple(shape[2:]):
             raise ValueError(f"mask must be [N, 1, *spatial] or [1, 1, *spatial] for an image of shape {tuple(shape)}, got {tuple(mask.shape)}")
 
+    @staticmethod
+    def _refuse_mask(mask):
+        if mask is not None:
+            raise ValueError("invert takes no mask: the inversion rows have no known region (use inpaint to regenerate one)")
+
     @torch.no_grad()
     def img2img(self, image, diffusion_model, strength, input_noise=None, scheduler=None, conditioning=None, mode="crossattn", verbose=True,
                 noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None, guidance_scale=None, null_class=None):
@@ -566,12 +609,8 @@ class DiffusionInferer:
         captured graph of `sample`; the other arguments as there (`noises`: one z per step taken)."""
         scheduler = scheduler or self.scheduler
         start = self._start(scheduler, strength)
-        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
-                                                                       null_class)
-        x = self._first_sample(image, input_noise, scheduler, start, generator)
-        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None, class_labels is not None)
-        return loop.run(x, noises=noises, generator=generator, use_graph=use_graph, conditioning=conditioning, eta=eta, class_labels=class_labels,
-                        guidance_scale=guidance_scale, null_class=null_class, start=start)
+        return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
+                         _Noise(noises, generator), input_noise, start, use_graph=use_graph, eta=eta)
 
     @torch.no_grad()
     def inpaint(self, image, mask, diffusion_model, strength=1.0, input_noise=None, known_noise=None, known_noises=None, resample=None,
@@ -594,19 +633,11 @@ class DiffusionInferer:
         start = self._start(scheduler, strength)
         if known_noise not in (None, "fixed", "fresh"):
             raise ValueError(f"known_noise must be 'fixed', 'fresh' or None, got {known_noise!r}")
-        n_steps = len(scheduler.timesteps)
-        moves = None if resample is None else resample_moves(n_steps, resample[0], resample[1], start)
-        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
-                                                                       null_class)
-        ddim = isinstance(scheduler, DDIMScheduler)
-        fresh = (not ddim or eta > 0) if known_noise is None else known_noise == "fresh"
-        x = self._first_sample(image, input_noise, scheduler, start, generator)
-        m = mask.to(device=image.device, dtype=F32).expand((image.shape[0],) + tuple(mask.shape[1:])).reshape(image.shape[0], -1).contiguous()
-        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None,
-                          class_labels is not None, inpaint=True)
-        return loop.run(x, noises=noises, generator=generator, use_graph=use_graph, on_step=on_step, conditioning=conditioning, eta=eta,
-                        class_labels=class_labels, guidance_scale=guidance_scale, null_class=null_class, start=start, moves=moves,
-                        image=image.float(), mask=m, fresh=fresh, known_noises=known_noises)
+        moves = None if resample is None else resample_moves(len(scheduler.timesteps), resample[0], resample[1], start)
+        fresh = (not isinstance(scheduler, DDIMScheduler) or eta > 0) if known_noise is None else known_noise == "fresh"
+        return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
+                         _Noise(noises, generator, known_noises, fresh), input_noise, start, mask, use_graph=use_graph, on_step=on_step,
+                         eta=eta, moves=moves)
 
     @torch.no_grad()
     def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True, class_labels=None,
@@ -614,16 +645,12 @@ class DiffusionInferer:
         """Image-to-noise DDIM inversion: DDIMScheduler.reversed_step over ascending timesteps in the fused loop of `sample` (same
         captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler.
         class_labels, guidance_scale, null_class: as in `sample`.  mask: refused -- there is no inversion of a masked region."""
-        if mask is not None:
-            raise ValueError("invert takes no mask: the inversion rows have no known region (use inpaint to regenerate one)")
+        self._refuse_mask(mask)
         scheduler = scheduler or self.scheduler
         if not isinstance(scheduler, DDIMScheduler):
             raise TypeError(f"invert needs a DDIMScheduler (reversed_step), not {type(scheduler).__name__}")
-        conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels, guidance_scale,
-                                                                       null_class)
-        loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None, class_labels is not None)
-        return loop.run(image.float(), use_graph=use_graph, conditioning=conditioning, reverse=True, class_labels=class_labels,
-                        guidance_scale=guidance_scale, null_class=null_class)
+        return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class, _Noise(), image,
+                         use_graph=use_graph, reverse=True)
 
 
 class LatentDiffusionInferer(DiffusionInferer):
@@ -658,8 +685,7 @@ class LatentDiffusionInferer(DiffusionInferer):
     def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True,
                class_labels=None, guidance_scale=None, null_class=None, mask=None):
         """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor)."""
-        if mask is not None:
-            raise ValueError("invert takes no mask: the inversion rows have no known region (use inpaint to regenerate one)")
+        self._refuse_mask(mask)
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
         return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class)
 

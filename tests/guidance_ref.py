@@ -1,5 +1,5 @@
 """fp64 restatement of classifier-free guidance (Ho & Salimans 2022; not part of the reference: PARITY UNPINNED) for the tests of
-`mi_ddpm_step_guided` / `mi_ddim_step_guided` and of the guided sample loop.  TEST INFRASTRUCTURE: written from the formula alone,
+the guided `mi_diffusion_step` and of the guided sample loop.  TEST INFRASTRUCTURE: written from the formula alone,
 on the oracle's fp32 U-Net and the fp64 DDIM rows of tests/ddim_ref.py; it does not import the product.
 
     m = m_uncond + w (m_cond - m_uncond)            w = 1: the conditional model, w = 0: the unconditional one

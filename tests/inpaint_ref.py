@@ -1,5 +1,5 @@
 """fp64 restatement of image-conditioned sampling (masked inpainting in the manner of RePaint, Lugmayr et al. 2022, and partial-noise
-starts; not part of the reference: PARITY UNPINNED) for the tests of `mi_step_inpaint`, `mi_renoise` and the inpaint / img2img loops.
+starts; not part of the reference: PARITY UNPINNED) for the tests of the composited `mi_diffusion_step`, `mi_renoise` and the inpaint / img2img loops.
 TEST INFRASTRUCTURE: written from the formulas alone, on the oracle's fp32 U-Net, the fp64 DDIM rows of tests/ddim_ref.py, the DDPM step
 of oracle/step.py and the guidance combination of tests/guidance_ref.py; it does not import the product.
 

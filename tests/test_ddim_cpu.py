@@ -1,6 +1,7 @@
 """inferer.DDIMScheduler on the CPU against the fp64 restatement in tests/ddim_ref.py (third-party closed form, PARITY UNPINNED -- see
 its docstring): timesteps, the per-step rows in both directions, the identity with the DDPM posterior that the mathematics gives,
 the tensor-level step / reversed_step, and the C-ABI surface of the fused update."""
+import ctypes
 import os
 import re
 
@@ -136,8 +137,10 @@ def test_fused_update_is_declared_and_bound():
     """The entry point is in the header and the binding with one argument list (tests/test_abi_cpu.py then checks the export)."""
     from medical_image_generation_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
-    m = re.search(r"\bint mi_ddim_step\s*\(([^)]*)\)\s*;", hdr)
-    assert m and "mi_ddim_step" in _lib._SIGS
-    assert len(m.group(1).split(",")) == len(_lib._SIGS["mi_ddim_step"])
-    assert _lib._SIGS["mi_ddim_step"] == _lib._SIGS["mi_ddpm_step"]  # same argument types; rows / row_index in place of coef / t
-    assert _lib.ABI_VERSION >= 14
+    m = re.search(r"\bint mi_diffusion_step\s*\(([^)]*)\)\s*;", hdr)
+    assert m and "mi_diffusion_step" in _lib._SIGS
+    assert len(m.group(1).split(",")) == len(_lib._SIGS["mi_diffusion_step"])
+    assert _lib._SIGS["mi_diffusion_step"][-2] is ctypes.c_int  # one entry for both schedulers: the ddim selector, before the stream
+    for old in ("mi_ddim_step", "mi_ddpm_step"):  # folded into it (ABI 20)
+        assert old not in _lib._SIGS and not re.search(r"\b%s\b" % old, hdr), old
+    assert _lib.ABI_VERSION >= 20

@@ -1,4 +1,4 @@
-"""DDIM few-step sampling and inversion on the HIP path (inferer.DDIMScheduler, `mi_ddim_step`) against the fp64 restatement in
+"""DDIM few-step sampling and inversion on the HIP path (inferer.DDIMScheduler, `mi_diffusion_step` with ddim = 1) against the fp64 restatement in
 tests/ddim_ref.py (third-party closed form, PARITY UNPINNED -- see its docstring): the fused update kernel per row, and the whole loop
 (UNet forward + update, hipGraph-replayed) against the same loop on the oracle's fp32 UNet.
 
@@ -24,7 +24,7 @@ N_INVERT = 5
 
 def test_ddim_step_kernel_matches_closed_form():
     """Shape (2, 3, 4, 6, 5): V = 120 is no multiple of the wave or the block.  The kernel reads the product's fp32 rows; the expected
-    values come from the restatement's fp64 rows.  Bounds as for `mi_ddpm_step`: fp32 x 1e-5 max(1, max|want|), bf16 copy 1e-2 max|want|."""
+    values come from the restatement's fp64 rows.  Bounds as for the DDPM form: fp32 x 1e-5 max(1, max|want|), bf16 copy 1e-2 max|want|."""
     from medical_image_generation_amd import hipops as ops
     from medical_image_generation_amd._lib import call, ptr
     from medical_image_generation_amd.inferer import DDIMScheduler
@@ -55,7 +55,8 @@ def test_ddim_step_kernel_matches_closed_form():
                         if cs:
                             x_cl = torch.zeros((N, 4, 6, 5, cs), dtype=torch.bfloat16, device="cuda")
                             x_cl[..., C:] = sentinel[..., :cs - C]
-                        call("mi_ddim_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(x_cl), cs, N, C, V, flags)
+                        call("mi_diffusion_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), None, None, None, None, None, ptr(x_cl), cs, N, C, V,
+                             flags, 1)
                         err = float((xd.cpu().double() - want).abs().max())
                         worst[0] = max(worst[0], err / tol)
                         assert err <= tol, (pred, clip, eta, reverse, i, cs, err, tol)
@@ -65,7 +66,7 @@ def test_ddim_step_kernel_matches_closed_form():
                             worst[1] = max(worst[1], err_cl / (1e-2 * float(want.abs().max())))
                             assert err_cl <= 1e-2 * float(want.abs().max()), (pred, clip, eta, reverse, i, cs, err_cl)
                             assert torch.equal(x_cl[..., C:].view(torch.int16), sentinel[..., :cs - C].view(torch.int16))  # the condition stays
-    print(f"\n[mi_ddim_step] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
+    print(f"\n[mi_diffusion_step ddim] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
     assert ddim_ref.rows(acp, n, 0.5)[5, 4] > 0 and ddim_ref.rows(acp, n, reverse=True)[n - 1, 2] == 0  # the rows are the ones meant
 
 
@@ -76,14 +77,15 @@ def test_ddim_step_kernel_refuses_bad_arguments():
     x_cl = torch.zeros(2, 120, 3, dtype=torch.bfloat16, device="cuda")
     rows = torch.ones(4, 5, device="cuda")
     idx = torch.zeros(1, dtype=torch.int64, device="cuda")
-    good = [ptr(x), ptr(mo), ptr(x), ptr(rows), ptr(idx), ptr(x_cl), 3, 2, 3, 120, 1]
-    for k in range(5):  # x, model_out, noise, rows, row_index
-        with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-            call("mi_ddim_step", *(good[:k] + [None] + good[k + 1:]))
-    for k, v in ((6, 2), (7, 0), (8, 0), (9, 0), (7, -1), (9, -5)):  # x_cl pitch below C; non-positive N, C, V
-        with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-            call("mi_ddim_step", *(good[:k] + [v] + good[k + 1:]))
-    call("mi_ddim_step", *good)  # (the unchanged arguments are accepted)
+    for ddim in (1, 0):  # the plain step of either form: no guidance, no known region
+        good = [ptr(x), ptr(mo), ptr(x), ptr(rows), ptr(idx), None, None, None, None, None, ptr(x_cl), 3, 2, 3, 120, 1, ddim]
+        for k in range(5):  # x, model_out, noise, rows, row_index
+            with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
+                call("mi_diffusion_step", *(good[:k] + [None] + good[k + 1:]))
+        for k, v in ((11, 2), (12, 0), (13, 0), (14, 0), (12, -1), (14, -5)):  # x_cl pitch below C; non-positive N, C, V
+            with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
+                call("mi_diffusion_step", *(good[:k] + [v] + good[k + 1:]))
+        call("mi_diffusion_step", *good)  # (the unchanged arguments are accepted)
     torch.cuda.synchronize()
 
 

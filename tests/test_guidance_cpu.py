@@ -13,7 +13,8 @@ from oracle import cases, synth
 from tests import guidance_ref as G
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("mi_ddpm_step_guided", "mi_ddim_step_guided", "mi_qsample_drop", "mi_select_labels", "mi_cast_bf16_drop")
+NEW = ("mi_qsample_drop", "mi_select_labels", "mi_cast_bf16_drop")
+FOLDED = ("mi_ddpm_step_guided", "mi_ddim_step_guided")  # the guided update is mi_diffusion_step with a non-NULL guidance (ABI 20)
 
 
 def test_library_exports_the_guidance_entry_points():
@@ -25,9 +26,10 @@ def test_library_exports_the_guidance_entry_points():
         m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % name, hdr)
         assert m, name
         assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
-    # the guided entries take the unguided argument list plus the pointer to the scale
-    assert len(_lib._SIGS["mi_ddim_step_guided"]) == len(_lib._SIGS["mi_ddim_step"]) + 1
-    assert _lib._SIGS["mi_ddim_step_guided"] == _lib._SIGS["mi_ddpm_step_guided"]
+    for name in FOLDED:
+        assert not hasattr(lib, name) and name not in _lib._SIGS and not re.search(r"\b%s\b" % name, hdr), name
+    m = re.search(r"\bint mi_diffusion_step\s*\(([^)]*)\)\s*;", hdr)
+    assert m and "const float* guidance" in m.group(1) and len(m.group(1).split(",")) == len(_lib._SIGS["mi_diffusion_step"])
     assert len(_lib._SIGS["mi_qsample_drop"]) == len(_lib._SIGS["mi_qsample"]) + 1
 
 

@@ -31,8 +31,8 @@ def _kernel_inputs():
     return x, z, mc, mu, mo_cl, z.cuda(), sentinel
 
 
-def _launch_and_check(entry, table, idx, wd, flags, want, cs, worst, what):
-    """One launch of a guided entry at x_cl pitch cs (0: no x_cl) and every check of its outputs."""
+def _launch_and_check(ddim, table, idx, wd, flags, want, cs, worst, what):
+    """One guided launch of `mi_diffusion_step` (no known region) at x_cl pitch cs (0: no x_cl) and every check of its outputs."""
     from medical_image_generation_amd import hipops as ops
     from medical_image_generation_amd._lib import call, ptr
     x, _, _, _, mo_cl, zd, sentinel = _kernel_inputs()
@@ -42,7 +42,8 @@ def _launch_and_check(entry, table, idx, wd, flags, want, cs, worst, what):
     if cs:
         x_cl = torch.zeros((2 * N, 4, 6, 5, cs), dtype=torch.bfloat16, device="cuda")
         x_cl[..., C:] = sentinel[..., :cs - C]
-    call(entry, ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), ptr(x_cl), cs, N, C, V, flags)
+    call("mi_diffusion_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), None, None, None, None, ptr(x_cl), cs, N, C, V, flags,
+         ddim)
     tol = 1e-5 * max(1.0, float(want.abs().max()))
     err = float((xd.cpu().double() - want).abs().max())
     worst[0] = max(worst[0], err / tol)
@@ -81,8 +82,8 @@ def test_ddim_step_guided_kernel_matches_closed_form():
                         wd.fill_(w)
                         want, _ = ddim_ref.update(want_rows[i], x, G.combine(mc, mu, w), z, prediction_type=pred, clip_sample=clip)
                         for cs in (C, C + 2, 0):
-                            _launch_and_check("mi_ddim_step_guided", table, idx, wd, flags, want, cs, worst, (pred, clip, eta, reverse, i, w))
-    print(f"\n[mi_ddim_step_guided] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
+                            _launch_and_check(1, table, idx, wd, flags, want, cs, worst, (pred, clip, eta, reverse, i, w))
+    print(f"\n[mi_diffusion_step ddim guided] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
     assert float((G.combine(mc, mu, 2.5) - mc.double()).abs().max()) > 1.0  # the halves differ: a swapped or dropped branch shows
 
 
@@ -108,12 +109,13 @@ def test_ddpm_step_guided_kernel_matches_closed_form():
                     want, _ = ref.step(G.combine(mc, mu, w), t, x.double(), z.double(), clip_sample=clip)
                     assert want.dtype == torch.float64
                     for cs in (C, C + 2, 0):
-                        _launch_and_check("mi_ddpm_step_guided", table, td, wd, flags, want, cs, worst, (pred, clip, t, w))
-    print(f"\n[mi_ddpm_step_guided] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
+                        _launch_and_check(0, table, td, wd, flags, want, cs, worst, (pred, clip, t, w))
+    print(f"\n[mi_diffusion_step ddpm guided] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
 
 
-@pytest.mark.parametrize("entry", ["mi_ddim_step_guided", "mi_ddpm_step_guided"])
-def test_guided_step_kernels_refuse_bad_arguments(entry):
+@pytest.mark.parametrize("ddim", [1, 0], ids=["ddim", "ddpm"])
+def test_guided_step_kernels_refuse_bad_arguments(ddim):
+    """What the guided entries refused, on the one entry that replaced them -- but a NULL guidance is the unguided step now."""
     from medical_image_generation_amd._lib import HipError, call, ptr
     x = torch.zeros(2, 3, 120, device="cuda")
     mo = torch.zeros(4, 120, 3, dtype=torch.bfloat16, device="cuda")
@@ -121,14 +123,14 @@ def test_guided_step_kernels_refuse_bad_arguments(entry):
     rows = torch.ones(4, 5, device="cuda")
     idx = torch.zeros(1, dtype=torch.int64, device="cuda")
     w = torch.ones(1, device="cuda")
-    good = [ptr(x), ptr(mo), ptr(x), ptr(rows), ptr(idx), ptr(w), ptr(x_cl), 3, 2, 3, 120, 1]
-    for k in range(6):  # x, model_out, noise, table, index, guidance
+    good = [ptr(x), ptr(mo), ptr(x), ptr(rows), ptr(idx), ptr(w), None, None, None, None, ptr(x_cl), 3, 2, 3, 120, 1, ddim]
+    for k in range(5):  # x, model_out, noise, table, index
         with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-            call(entry, *(good[:k] + [None] + good[k + 1:]))
-    for k, v in ((7, 2), (8, 0), (9, 0), (10, 0), (8, -1), (10, -5)):  # x_cl pitch below C; non-positive N, C, V
+            call("mi_diffusion_step", *(good[:k] + [None] + good[k + 1:]))
+    for k, v in ((11, 2), (12, 0), (13, 0), (14, 0), (12, -1), (14, -5)):  # x_cl pitch below C; non-positive N, C, V
         with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-            call(entry, *(good[:k] + [v] + good[k + 1:]))
-    call(entry, *good)  # (the unchanged arguments are accepted)
+            call("mi_diffusion_step", *(good[:k] + [v] + good[k + 1:]))
+    call("mi_diffusion_step", *good)  # (the unchanged arguments are accepted)
     torch.cuda.synchronize()
 
 

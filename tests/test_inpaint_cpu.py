@@ -1,5 +1,5 @@
 """CPU side of image-conditioned sampling (inpaint / img2img; not part of the reference: PARITY UNPINNED): the C-ABI surface of
-`mi_step_inpaint` / `mi_renoise`, the schedulers' known rows against the fp64 restatement (tests/inpaint_ref.py), the move lists of
+`mi_diffusion_step` / `mi_renoise`, the schedulers' known rows against the fp64 restatement (tests/inpaint_ref.py), the move lists of
 `resample_moves` against hand-written ones, the strength-to-start mapping, and every refusal that needs no GPU."""
 import ctypes
 import os
@@ -23,15 +23,17 @@ def test_library_exports_the_inpaint_entry_points():
     from medical_image_generation_amd import _lib
     lib = ctypes.CDLL(_lib.LIB_PATH)
     hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
-    for name in ("mi_step_inpaint", "mi_renoise"):
+    for name in ("mi_diffusion_step", "mi_renoise"):
         assert hasattr(lib, name), name
         m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % name, hdr)
         assert m, name
         assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
-    # the guided argument list + mask, image, known_noise, known + the ddim selector
-    assert len(_lib._SIGS["mi_step_inpaint"]) == len(_lib._SIGS["mi_ddim_step_guided"]) + 5
+    # x, model_out, noise, table, index, guidance + mask, image, known_noise, known + x_cl, its pitch, N, C, V, flags + ddim + the stream
+    assert len(_lib._SIGS["mi_diffusion_step"]) == 6 + 4 + 6 + 1 + 1
     assert _lib._SIGS["mi_renoise"][2:4] == [ctypes.c_float, ctypes.c_float]  # a, b by value
-    assert _lib.ABI_VERSION == 19 and lib.mi_abi_version() == 19
+    for old in ("mi_ddpm_step", "mi_ddim_step", "mi_ddpm_step_guided", "mi_ddim_step_guided", "mi_step_inpaint"):  # the five it replaced
+        assert not hasattr(lib, old) and old not in _lib._SIGS and not re.search(r"\b%s\b" % old, hdr), old
+    assert _lib.ABI_VERSION == 20 and lib.mi_abi_version() == 20
 
 
 @pytest.mark.parametrize("n,eta", [(1000, 0.0), (10, 0.0), (10, 0.5), (7, 1.0)])

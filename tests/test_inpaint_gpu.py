@@ -1,6 +1,6 @@
 """Image-conditioned sampling on the HIP path (masked inpainting in the manner of RePaint, partial-noise starts, resampling; not part of
-the reference: PARITY UNPINNED): `mi_step_inpaint` and `mi_renoise` against the fp64 restatement (tests/inpaint_ref.py on
-tests/ddim_ref.py, oracle/step.py and tests/guidance_ref.py) and, bit for bit, against the step kernels they extend; the inpaint /
+the reference: PARITY UNPINNED): the composited `mi_diffusion_step` and `mi_renoise` against the fp64 restatement (tests/inpaint_ref.py on
+tests/ddim_ref.py, oracle/step.py and tests/guidance_ref.py) and, bit for bit, against the plain step it extends; the inpaint /
 img2img loops against the same loops on the oracle's fp32 U-Net, at the nets, schedule and budget of tests/test_ddim_gpu.py."""
 import functools
 
@@ -48,7 +48,7 @@ def _vox(mask):
 
 
 def _launch(ddim, table, known, idx, flags, mask, cs, guided, t=None):
-    """One mi_step_inpaint launch at x_cl pitch cs (0: no x_cl) on the inputs t (default: _inputs()) -> (x, x_cl or None) after it."""
+    """One composited mi_diffusion_step launch at x_cl pitch cs (0: no x_cl) on the inputs t (default: _inputs()) -> (x, x_cl or None) after it."""
     from medical_image_generation_amd import hipops as ops
     from medical_image_generation_amd._lib import call, ptr
     t = t or _inputs()
@@ -60,7 +60,7 @@ def _launch(ddim, table, known, idx, flags, mask, cs, guided, t=None):
     if cs:
         x_cl = torch.zeros((nb, 4, 6, 5, cs), dtype=torch.bfloat16, device="cuda")
         x_cl[..., C:] = _inputs()["sentinel"][:nb, ..., :cs - C]
-    call("mi_step_inpaint", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), ptr(md), ptr(imd), ptr(zkd), ptr(known), ptr(x_cl), cs,
+    call("mi_diffusion_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), ptr(md), ptr(imd), ptr(zkd), ptr(known), ptr(x_cl), cs,
          N, C, V, flags, int(ddim))
     torch.cuda.synchronize()
     return xd, x_cl
@@ -141,7 +141,7 @@ def test_ddim_step_inpaint_kernel_matches_closed_form():
                 want = _want(gen, krow, mask)
                 for cs in (C, C + 2, 0):
                     _check(_launch(True, table, known, idx, flags, mask, cs, guided), want, cs, guided, worst, (pred, clip, eta, i, guided))
-    print(f"\n[mi_step_inpaint ddim] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
+    print(f"\n[mi_diffusion_step ddim inpaint] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
 
 
 def test_ddpm_step_inpaint_kernel_matches_closed_form():
@@ -159,11 +159,11 @@ def test_ddpm_step_inpaint_kernel_matches_closed_form():
                 want = _want(gen, krow, mask)
                 for cs in (C, C + 2, 0):
                     _check(_launch(False, table, known, td, flags, mask, cs, guided), want, cs, guided, worst, (pred, clip, ts, guided))
-    print(f"\n[mi_step_inpaint ddpm] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
+    print(f"\n[mi_diffusion_step ddpm inpaint] worst error / bound: fp32 {worst[0]:.3f}, bf16 copy {worst[1]:.3f}")
 
 
 def _plain_step(ddim, table, idx, flags, cs, guided):
-    """The existing entry on the same inputs -> (x, x_cl)."""
+    """The plain step -- the same entry with no known region: another kernel around the same body -- on the same inputs -> (x, x_cl)."""
     from medical_image_generation_amd import hipops as ops
     from medical_image_generation_amd._lib import call, ptr
     t = _inputs()
@@ -172,19 +172,19 @@ def _plain_step(ddim, table, idx, flags, cs, guided):
     xd, zd = t["x"].cuda(), t["z"].cuda()
     x_cl = torch.zeros((nb, 4, 6, 5, cs), dtype=torch.bfloat16, device="cuda")
     x_cl[..., C:] = t["sentinel"][:nb, ..., :cs - C]
-    if guided:
-        wd = torch.full((1,), W_KERNEL, device="cuda")
-        call("mi_ddim_step_guided" if ddim else "mi_ddpm_step_guided", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), ptr(x_cl), cs,
-             N, C, V, flags)
-    else:
-        call("mi_ddim_step" if ddim else "mi_ddpm_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(x_cl), cs, N, C, V, flags)
+    wd = torch.full((1,), W_KERNEL, device="cuda") if guided else None
+    call("mi_diffusion_step", ptr(xd), ptr(mo_cl), ptr(zd), ptr(table), ptr(idx), ptr(wd), None, None, None, None, ptr(x_cl), cs, N, C, V, flags,
+         int(ddim))
     torch.cuda.synchronize()
     return xd, x_cl
 
 
 def test_mask_one_voxels_carry_the_bits_of_the_plain_kernels():
     """Every case of the two tests above at pitch C + 2, mask A (sample 1 all 1, a third of sample 0): where the mask is 1, x and its bf16
-    copy torch.equal the output of mi_ddim_step / mi_ddpm_step / the guided entries on the same inputs."""
+    copy torch.equal the output of the plain step, unguided and guided, on the same inputs.  Both launches go through
+    mi_diffusion_step, with and without the mask / image / known_noise / known quadruple: these are different kernels
+    (k_diffusion_step / k_diffusion_step_guided against k_diffusion_step_inpaint, one device body instantiated with INPAINT off and on),
+    so the comparison is still between separately compiled code."""
     mask = _masks()[0]
     sel = (_vox(mask) >= 1).expand(SHAPE).cuda()           # NCDHW
     sel_cl = sel.permute(0, 2, 3, 4, 1)                     # NDHWC
@@ -282,12 +282,16 @@ def test_inpaint_kernels_refuse_bad_arguments():
         good = [ptr(x), ptr(mo), ptr(x), ptr(rows), ptr(idx), ptr(w), ptr(mask), ptr(x), ptr(x), ptr(known), ptr(x_cl), 3, 2, 3, 120, 1, ddim]
         for k in (0, 1, 2, 3, 4, 6, 7, 8, 9):  # x, model_out, noise, table, index, mask, image, known_noise, known (guidance may be NULL)
             with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-                call("mi_step_inpaint", *(good[:k] + [None] + good[k + 1:]))
+                call("mi_diffusion_step", *(good[:k] + [None] + good[k + 1:]))
+        for gone in ((6, 7), (8, 9), (6, 9), (7, 8, 9), (6, 7, 8), (6, 8, 9)):  # the known region is given whole or not at all
+            with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
+                call("mi_diffusion_step", *[None if k in gone else a for k, a in enumerate(good)])
         for k, v in ((11, 2), (12, 0), (13, 0), (14, 0), (12, -1), (14, -5)):  # x_cl pitch below C; non-positive N, C, V
             with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):
-                call("mi_step_inpaint", *(good[:k] + [v] + good[k + 1:]))
-        call("mi_step_inpaint", *good)  # (the unchanged arguments are accepted,
-        call("mi_step_inpaint", *(good[:5] + [None] + good[6:]))  # and so is a NULL guidance: the unguided step)
+                call("mi_diffusion_step", *(good[:k] + [v] + good[k + 1:]))
+        call("mi_diffusion_step", *good)  # (the unchanged arguments are accepted,
+        call("mi_diffusion_step", *(good[:5] + [None] + good[6:]))  # and so are a NULL guidance: the unguided step,
+        call("mi_diffusion_step", *(good[:6] + [None] * 4 + good[10:]))  # and no known region at all: the plain step)
     good = [ptr(x), ptr(x), 0.5, 0.5, ptr(x_cl), 3, 2, 2, 3, 120]
     for k in (0, 1):
         with pytest.raises(HipError, match="MI_ERR_BAD_ARG"):

@@ -156,7 +156,7 @@ def test_library_exports_the_preprocess_entry_points():
         assert m, name
         assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
     assert "resample_image_label 1105-1167" in hdr and "configuration.py:1133-1155" in hdr  # the declarations cite the reference lines they replace
-    assert _lib.ABI_VERSION == 19 and lib.mi_abi_version() == 19  # entry points were added, no argument list changed
+    assert _lib.ABI_VERSION == 20 and lib.mi_abi_version() == 20  # 19 with these entry points; 20: the sampler's step entries became one
     src = open(os.path.join(ROOT, "medical_image_generation_amd", "csrc", "Makefile")).read()
     assert re.search(r"^SRC\s*:=.*\bpreprocess\.hip\b", src, re.M)
 

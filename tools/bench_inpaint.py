@@ -3,7 +3,7 @@ LDM configs (C3b) at 4 x 8 x 32^3, DDIM with eta 0, graph replay.
 
     loop     ms per denoising step of `sample` and of `inpaint` (half of the volume masked, fixed known noise): host clock around the
              call, ending in a device synchronise, the two alternated `--repeats` times in one process after a warm-up call each
-    launch   the update launch alone, `mi_ddim_step` against `mi_step_inpaint` with a mask of all 1, all 0, a contiguous half and all
+    launch   the update launch alone (`mi_diffusion_step`, DDIM), plain against composited with a mask of all 1, all 0, a contiguous half and all
              0.5 (every buffer read), on an eta-1 row (z is read): HIP events around `--launches` launches that walk over sets of
              buffers -- so many that what the plain launch touches exceeds `--footprint-mib` (default 384, above the 256 MiB of
              Infinity Cache: a launch reads from HBM, as it does behind a forward) --, alternated `--repeats` times; GB/s = the
@@ -85,14 +85,14 @@ def launches(name, shape, a):
     idx = torch.full((1,), 25, dtype=torch.int64, device="cuda")
     assert float(table[25, 4]) > 0  # z is read
     el = n * c * v
-    n_sets = a.footprint_mib * 2 ** 20 // (el * 12) + 1  # x, model output, z, x_cl: what mi_ddim_step touches
+    n_sets = a.footprint_mib * 2 ** 20 // (el * 12) + 1  # x, model output, z, x_cl: what the plain step touches
     sets = []
     for _ in range(n_sets):
         sets.append(dict(x=torch.randn(n, c, v, device="cuda"), mo=torch.randn(n, v, c, device="cuda").bfloat16(), z=torch.randn(n, c, v, device="cuda"),
                          x_cl=torch.zeros(n, v, c, dtype=torch.bfloat16, device="cuda"), image=torch.randn(n, c, v, device="cuda"),
                          zk=torch.randn(n, c, v, device="cuda"), mask=torch.ones(n, v, device="cuda")))
     gen, kept, m = 4 + 2 + 4 + 4 + 2, 4 + 4 + 4 + 2, 4.0 / c  # bytes per element: x, model output, z in, x, x_cl out | image, zk in, x, x_cl out | mask
-    variants = {"mi_ddim_step": (None, gen), "inpaint mask 1": (1.0, gen + m), "inpaint mask 0": (0.0, kept + m),
+    variants = {"plain": (None, gen), "inpaint mask 1": (1.0, gen + m), "inpaint mask 0": (0.0, kept + m),
                 "inpaint half": ("half", (gen + kept) / 2 + m), "inpaint mask 0.5": (0.5, gen + 4 + 4 + m)}
 
     def fill(value):
@@ -108,11 +108,8 @@ def launches(name, shape, a):
         e0.record()
         for k in range(a.launches):
             s = sets[k % n_sets]
-            if value is None:
-                call("mi_ddim_step", ptr(s["x"]), ptr(s["mo"]), ptr(s["z"]), ptr(table), ptr(idx), ptr(s["x_cl"]), c, n, c, v, 1)
-            else:
-                call("mi_step_inpaint", ptr(s["x"]), ptr(s["mo"]), ptr(s["z"]), ptr(table), ptr(idx), None, ptr(s["mask"]), ptr(s["image"]),
-                     ptr(s["zk"]), ptr(known), ptr(s["x_cl"]), c, n, c, v, 1, 1)
+            region = [None] * 4 if value is None else [ptr(s["mask"]), ptr(s["image"]), ptr(s["zk"]), ptr(known)]  # NULL: the plain step
+            call("mi_diffusion_step", ptr(s["x"]), ptr(s["mo"]), ptr(s["z"]), ptr(table), ptr(idx), None, *region, ptr(s["x_cl"]), c, n, c, v, 1, 1)
         e1.record()
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) / a.launches * 1e3  # microseconds per launch
@@ -131,7 +128,7 @@ def launches(name, shape, a):
                           us_min_max={k: [round(min(t), 2), round(max(t), 2)] for k, t in times.items()},
                           bytes_per_element={k: round(b, 2) for k, (_, b) in variants.items()},
                           gb_per_s={k: round(el * variants[k][1] / (med[k] * 1e-6) / 1e9, 1) for k in variants},
-                          over_plain={k: round(med[k] / med["mi_ddim_step"], 3) for k in variants})), flush=True)
+                          over_plain={k: round(med[k] / med["plain"], 3) for k in variants})), flush=True)
     del sets
     torch.cuda.empty_cache()
 
