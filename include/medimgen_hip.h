@@ -547,6 +547,29 @@ int mi_pp_box_stats(const float* x, int X, int Y, int Z, int C, int x0, int y0, 
 int mi_pp_finish_image(const float* x, float* out, int X, int Y, int Z, int C, int x0, int y0, int z0, int nx, int ny, int nz, const float* lo_inv, hipStream_t stream);
 int mi_pp_finish_label(const uint8_t* label, uint8_t* out, int X, int Y, int Z, int x0, int y0, int z0, int nx, int ny, int nz, hipStream_t stream);
 
+/* ---- sliding-window inference (sliding.py: the swap for monai.inferers.SlidingWindowInferer, restated there; PARITY UNPINNED): a
+ * patch-trained network run over a whole case.  fp32 NC[D]HW, 2-D as D = 1.  Extents and window origins are read from a device
+ * `table` of int32 [1 + B][4]: row 0 = N, D, H, W of the image (gather) or of the accumulator (accumulate), row 1 + b = n, z0, y0, x0
+ * of window b; n < 0 marks a filler row.  They are no launch constants: a captured graph serves every case extent.  `host_table`
+ * (host memory, may be NULL) is the caller's copy of the same table; when given it is validated (MI_ERR_BAD_ARG) before anything is
+ * launched.  The kernels guard themselves either way: a table whose tensor would exceed `*_elems`, a row with n >= N and (accumulate)
+ * a window that leaves the accumulator write nothing (gather: zeros).
+ *   mi_sw_gather: tiles[b][c][z][y][x] = image[n][c][z0 + z][y0 + y][x0 + x]; origins count from the image's first voxel and may be
+ *     negative (the padded border lies outside [0, extent)).  Outside voxels: MI_SW_PAD_CONSTANT -> cval, MI_SW_PAD_REFLECT (mirror
+ *     without edge repeat; host_table: a pad >= the axis extent is MI_ERR_BAD_ARG), MI_SW_PAD_REPLICATE.  Filler rows: zeros.
+ *   mi_sw_accumulate: for b = 0 .. B-1 in order, valid rows only: acc[n][:][window] += imp * pred[b] (one fused multiply-add per
+ *     term), and for n == 0 also wsum[window] += imp; pred [B][Co][td][th][tw], imp [td][th][tw], acc [N][Co][D][H][W], wsum
+ *     [D][H][W].  One launch per row in stream order, no atomics: the sum over windows is in enumeration order whatever B is.
+ *   mi_sw_finish: out[n][c][z][y][x] = acc[n][c][pd + z][ph + y][pw + x] / wsum[pd + z][ph + y][pw + x] (IEEE division), out dense
+ *     [N][Co][fd][fh][fw]; the crop must lie inside the accumulator.
+ * All three move 16 bytes per access along W where origin, pitch and pointers are multiples of four floats, single floats elsewhere. */
+#define MI_SW_PAD_CONSTANT 0
+#define MI_SW_PAD_REFLECT 1
+#define MI_SW_PAD_REPLICATE 2
+int mi_sw_gather(const float* image, int64_t image_elems, int C, const int* table, const int* host_table, int B, int rd, int rh, int rw, int mode, float cval, float* tiles, hipStream_t stream);
+int mi_sw_accumulate(const float* pred, const float* imp, const int* table, const int* host_table, int B, int Co, int td, int th, int tw, float* acc, float* wsum, int64_t acc_elems, hipStream_t stream);
+int mi_sw_finish(const float* acc, const float* wsum, float* out, int N, int Co, int D, int H, int W, int pd, int ph, int pw, int fd, int fh, int fw, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

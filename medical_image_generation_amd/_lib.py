@@ -144,6 +144,9 @@ _SIGS = {
     "mi_pp_box_stats": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
     "mi_pp_finish_image": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
     "mi_pp_finish_label": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "mi_sw_gather": [_p, _l, _i, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p],
+    "mi_sw_accumulate": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p],
+    "mi_sw_finish": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l,
         "mi_pp_stats_workspace_bytes": _l}
@@ -179,7 +182,11 @@ def load():
             raise RuntimeError(f"{LIB_PATH} is a stale library (C ABI {have}, this binding needs {ABI_VERSION}): rebuild it with "
                                "`python -c 'import __graft_entry__ as g; g.build()'`")
         for name, args in _SIGS.items():
-            fn = getattr(lib, name)  # AttributeError here = header/library mismatch
+            try:
+                fn = getattr(lib, name)
+            except AttributeError:  # entry points added without a version change (mi_sw_*): a library built before them is stale too
+                raise RuntimeError(f"{LIB_PATH} is a stale library (it lacks {name}): rebuild it with "
+                                   "`python -c 'import __graft_entry__ as g; g.build()'`") from None
             fn.argtypes = args
             fn.restype = _RET.get(name, _i)
         _lib = lib

@@ -655,11 +655,21 @@ class DiffusionInferer:
 
 class LatentDiffusionInferer(DiffusionInferer):
     """`generative.inferers.LatentDiffusionInferer(scheduler, scale_factor)`: samples latents, then decodes
-    `autoencoder_model.decode_stage_2_outputs(latents / scale_factor)` (train_ldm.py:112, 362-364)."""
+    `autoencoder_model.decode_stage_2_outputs(latents / scale_factor)` (train_ldm.py:112, 362-364).
+
+    `decode_inferer=` on sample / img2img / inpaint (not part of upstream): a `sliding.SlidingWindowInferer` whose roi_size is in
+    latent voxels; the final decode then runs window by window (`sliding.tiled_decode`), for latents larger than the patch the
+    autoencoder was trained on.  None: the plain decode."""
 
     def __init__(self, scheduler, scale_factor=1.0):
         super().__init__(scheduler)
         self.scale_factor = scale_factor
+
+    def _decode(self, autoencoder_model, latent, decode_inferer=None):
+        if decode_inferer is None:
+            return autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
+        from .sliding import tiled_decode  # here, not at the top: the trainers import this module and tile nothing
+        return tiled_decode(autoencoder_model, latent / self.scale_factor, decode_inferer)
 
     def __call__(self, inputs, autoencoder_model, diffusion_model, noise, timesteps, condition=None, mode="crossattn"):
         """`generative.inferers.LatentDiffusionInferer.__call__`: encode (no grad) -> * scale_factor -> DiffusionInferer.__call__."""
@@ -671,14 +681,14 @@ class LatentDiffusionInferer(DiffusionInferer):
     @torch.no_grad()
     def sample(self, input_noise, autoencoder_model, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100,
                conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
-               guidance_scale=None, null_class=None):
+               guidance_scale=None, null_class=None, decode_inferer=None):
         out = super().sample(input_noise, diffusion_model, scheduler, save_intermediates, intermediate_steps, conditioning, mode, verbose,
                              noises=noises, generator=generator, use_graph=use_graph, eta=eta, class_labels=class_labels,
                              guidance_scale=guidance_scale, null_class=null_class)
         latent, inter = out if save_intermediates else (out, None)
-        image = autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
+        image = self._decode(autoencoder_model, latent, decode_inferer)
         if save_intermediates:
-            return image, [autoencoder_model.decode_stage_2_outputs(z / self.scale_factor) for z in inter]
+            return image, [self._decode(autoencoder_model, z, decode_inferer) for z in inter]
         return image
 
     @torch.no_grad()
@@ -690,11 +700,11 @@ class LatentDiffusionInferer(DiffusionInferer):
         return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class)
 
     @torch.no_grad()
-    def img2img(self, image, autoencoder_model, diffusion_model, strength, input_noise=None, **kwargs):
+    def img2img(self, image, autoencoder_model, diffusion_model, strength, input_noise=None, decode_inferer=None, **kwargs):
         """DiffusionInferer.img2img on encode_stage_2_inputs(image) * scale_factor (input_noise has the latent's shape), then decoded."""
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
         latent = super().img2img(latent, diffusion_model, strength, input_noise, **kwargs)
-        return autoencoder_model.decode_stage_2_outputs(latent / self.scale_factor)
+        return self._decode(autoencoder_model, latent, decode_inferer)
 
     @staticmethod
     def latent_mask(mask, latent_spatial):
@@ -708,14 +718,15 @@ class LatentDiffusionInferer(DiffusionInferer):
         return pool(mask.float(), kernel_size=f, stride=f)
 
     @torch.no_grad()
-    def inpaint(self, image, mask, autoencoder_model, diffusion_model, strength=1.0, input_noise=None, paste_back=True, **kwargs):
+    def inpaint(self, image, mask, autoencoder_model, diffusion_model, strength=1.0, input_noise=None, paste_back=True, decode_inferer=None,
+                **kwargs):
         """DiffusionInferer.inpaint in the latent space: the image encoded (* scale_factor), the mask reduced by `latent_mask` (once per
         call), the loop, then decoded.  paste_back: return mask * decoded + (1 - mask) * image in image space -- the autoencoder is
         lossy, and known voxels must come back exactly.  input_noise and the pinned noises have the latent's shape."""
         self._check_mask(mask, image.shape)
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
         out = super().inpaint(latent, self.latent_mask(mask, latent.shape[2:]), diffusion_model, strength, input_noise, **kwargs)
-        out = autoencoder_model.decode_stage_2_outputs(out / self.scale_factor)
+        out = self._decode(autoencoder_model, out, decode_inferer)
         if paste_back:
             m = mask.to(device=out.device, dtype=out.dtype)
             out = m * out + (1 - m) * image.to(out.dtype)
