@@ -570,6 +570,26 @@ int mi_sw_gather(const float* image, int64_t image_elems, int C, const int* tabl
 int mi_sw_accumulate(const float* pred, const float* imp, const int* table, const int* host_table, int B, int Co, int td, int th, int tw, float* acc, float* wsum, int64_t acc_elems, hipStream_t stream);
 int mi_sw_finish(const float* acc, const float* wsum, float* out, int N, int Co, int D, int H, int W, int pd, int ph, int pw, int fd, int fh, int fw, hipStream_t stream);
 
+/* ---- tiled diffusion sampling (inferer.py `window_inferer=`: MultiDiffusion, Bar-Tal et al. 2023; not part of the reference: PARITY
+ * UNPINNED): at every reverse-diffusion step the model runs on overlapping windows of its training extent, the window predictions are
+ * blended with the importance map, and the scheduler's update is applied to the whole case.  The sample x and the accumulator acc are
+ * fp32 NC[D]HW, the model's input and output are NDHWC bf16 window batches; `table` / `host_table` as above, row 0 = N, D, H, W of the
+ * case.  There is no padding: a row whose window does not lie inside the case is a filler like n < 0 (host_table: MI_ERR_BAD_ARG).
+ *   mi_sw_gather_cl: out[b][z][y][x][c] = bf16(x[n][c][z0 + z][y0 + y][x0 + x]) for c < C and bf16(cond[n][c - C][...]) behind them
+ *     (cond fp32 [N][Cc][D][H][W], NULL with Cc = 0): the model input, C + Cc channels per voxel, rounded as mi_ncdhw_f32_to_ndhwc_bf16
+ *     rounds.  Filler rows: zeros.  guided != 0: out has 2 B rows, rows [B, 2B) repeat the sample channels with zero condition channels.
+ *   mi_sw_accumulate_cl: for b = 0 .. B-1 in order, valid rows only: acc[n][c][window] += imp * p_b[c] (one fused multiply-add per
+ *     term), p_b = pred[b] read as fp32 -- or, with guidance (device pointer to the scale w; pred then has 2 B rows, [B, 2B) under the
+ *     null condition), p_b = pred[B + b] + w (pred[b] - pred[B + b]), the expression of mi_diffusion_step, formed per window before the
+ *     blend.  pred [B or 2B][td][th][tw][Co] bf16, imp [td][th][tw].  wsum (may be NULL) as mi_sw_accumulate; pred NULL: wsum alone.
+ *     One launch per row in stream order, no atomics: the sum does not depend on B.
+ *   mi_sw_diffusion_step: m = acc / wsum[voxel] (IEEE division), x = the update of mi_diffusion_step's plain form on (x, m, noise, row
+ *     index[0] of table, flags, ddim) -- the same device functions --, acc = 0.  acc [N][C][V], wsum [V].
+ * 16 bytes per access on the fp32 side where origin, pitch and pointers are multiples of four floats, single floats elsewhere. */
+int mi_sw_gather_cl(const float* x, int64_t x_elems, int C, const float* cond, int64_t cond_elems, int Cc, const int* table, const int* host_table, int B, int guided, int rd, int rh, int rw, void* out, hipStream_t stream);
+int mi_sw_accumulate_cl(const void* pred, const float* guidance, const float* imp, const int* table, const int* host_table, int B, int Co, int td, int th, int tw, float* acc, float* wsum, int64_t acc_elems, hipStream_t stream);
+int mi_sw_diffusion_step(float* x, float* acc, const float* wsum, const float* noise, const float* table, const int64_t* index, int N, int C, int64_t V, int flags, int ddim, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -147,6 +147,9 @@ _SIGS = {
     "mi_sw_gather": [_p, _l, _i, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p],
     "mi_sw_accumulate": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p],
     "mi_sw_finish": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
+    "mi_sw_gather_cl": [_p, _l, _i, _p, _l, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p],
+    "mi_sw_accumulate_cl": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p],
+    "mi_sw_diffusion_step": [_p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l,
         "mi_pp_stats_workspace_bytes": _l}
@@ -184,7 +187,7 @@ def load():
         for name, args in _SIGS.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:  # entry points added without a version change (mi_sw_*): a library built before them is stale too
+            except AttributeError:  # entry points added without a version change (mi_sw_*, then mi_sw_*_cl / mi_sw_diffusion_step): a library built before them is stale too
                 raise RuntimeError(f"{LIB_PATH} is a stale library (it lacks {name}): rebuild it with "
                                    "`python -c 'import __graft_entry__ as g; g.build()'`") from None
             fn.argtypes = args

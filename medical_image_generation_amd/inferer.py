@@ -30,11 +30,35 @@ mask is 1, the known image at the level the step arrives at where it is 0 (a per
 Resampling is a list of moves: denoising steps, replayed from the same graph, and forward-diffusion moves (`mi_renoise`) between them.
 Mask, image and known-region noise are buffers, the known rows a table the captured step already points at; the start and the move list
 only choose which replays happen: one captured graph serves every run-time choice.
+
+Tiled sampling (`window_inferer=` on sample / img2img / invert; MultiDiffusion, Bar-Tal et al. 2023 -- not part of the reference; PARITY
+UNPINNED; off unless called): a whole case from a patch-trained U-Net.  At every step the model runs on overlapping windows of its
+training extent, the window predictions are blended, and the scheduler's update is applied to the whole case.  Given the sample x fp32
+[N, C, *S], an optional concat condition cond [N, Cc, *S], the windows o_k and extent roi of sliding.WindowPlan(S, roi_size, overlap),
+the importance map imp (fp32, built as SlidingWindowInferer builds it), the model f and a step at timestep t:
+
+    p_k      = f(cat(x[n, :, o_k : o_k+roi], cond[n, :, o_k : o_k+roi]), t, context_n, label_n)   # bf16 NDHWC model output, read as fp32
+    guided:    p_k = p_k(null condition) + w * (p_k(condition) - p_k(null condition))             # per window, before the blend, fp32
+    acc[n,c,v] = sum_k imp[v-o_k] * p_k[c, v-o_k]
+    wsum[v]    = sum_k imp[v-o_k]
+    m[n,c,v]   = acc[n,c,v] / wsum[v]                                                             # IEEE division
+    x[n,c,v]  <- ddpm_update / ddim_update(x, m, z, row of this step)
+
+Each term of acc is one fused multiply-add, in flat window order n * num_windows + w, as `mi_sw_accumulate` does it; wsum sums in the
+same order.  The update is the plain step's own arithmetic (the same device functions, flags, table row and device scalar index), so one
+window that covers the case in mode="constant" is the plain sampler bit for bit.  There is no padding: a case smaller than roi on any axis
+is a ValueError, because a noise sample has no border to mirror.  wsum does not change during a run and is computed once per run.
+Filler rows of the last window batch run the model on zeros and are never accumulated.  Class labels and context rows belong to each
+window's image n and are staged per window batch like the table rows.  The voxel passes are `mi_sw_gather_cl` (the model input of a
+window batch straight from x and cond), `mi_sw_accumulate_cl` (blend, guided combination first) and `mi_sw_diffusion_step` (division,
+update, acc = 0) in csrc/sliding.hip; one captured gather -> U-Net -> accumulate body is replayed per window batch (`_TiledLoop`), so
+eager and captured runs are bit-equal and nothing synchronises with the host inside a run.  `inpaint` is not tiled.
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 
 from . import engine as E
@@ -335,20 +359,15 @@ class _Loop:
         self.m, self.sch = model, scheduler
         n, c = shape[0], shape[1]
         self.guided = bool(guided)
-        nb = 2 * n if self.guided else n  # the model's batch
         sp = tuple(shape[2:])
         self.v = math.prod(sp)
-        dims = (1,) * (3 - len(sp)) + sp
         self.n, self.c = n, c
         self.x = torch.empty(shape, dtype=F32, device=device)                    # the sample, fp32 NC[D]HW
         self.cc = int(cond_channels)
-        self.x_cl = torch.empty((nb,) + dims + (c + self.cc,), dtype=torch.bfloat16, device=device)  # ... as the model reads it (+ condition)
-        self.ctx = None if context_shape is None else torch.empty((nb * context_shape[0], context_shape[1]), dtype=torch.bfloat16, device=device)
-        self.labels = torch.zeros(nb, dtype=torch.int64, device=device) if labels else None
+        self._model_buffers(n, sp, device, context_shape, labels)
         self.w = torch.ones(1, dtype=F32, device=device) if self.guided else None  # the guidance scale the guided update kernel reads
         self.z = torch.empty(shape, dtype=F32, device=device)
         self.t = torch.zeros(1, dtype=torch.int64, device=device)   # what the update kernel indexes its tables with (scheduler._index)
-        self.tn = torch.zeros(nb, dtype=torch.int64, device=device)  # the timestep the model reads
         self.coef = scheduler.coefficients(device)
         self.inpaint = bool(inpaint)
         self.image = self.mask = self.zk = self.known = None
@@ -361,6 +380,25 @@ class _Loop:
         self.graph = None
         self.keys = ()  # conv plans whose weights are packed: once per run(), not per step (the weights do not change while sampling)
         self._pinned = None  # objects whose device memory the captured graph points at (conv plans, GroupNorm workspace)
+        self.captures = 0
+
+    def _model_buffers(self, rows, sp, device, context_shape, labels):
+        """What the model reads: `rows` samples of spatial extent `sp` (twice as many when guided)."""
+        nb = 2 * rows if self.guided else rows  # the model's batch
+        dims = (1,) * (3 - len(sp)) + tuple(sp)
+        self.x_cl = torch.empty((nb,) + dims + (self.c + self.cc,), dtype=torch.bfloat16, device=device)  # the sample as the model reads it (+ condition)
+        self.ctx = None if context_shape is None else torch.empty((nb * context_shape[0], context_shape[1]), dtype=torch.bfloat16, device=device)
+        self.labels = torch.zeros(nb, dtype=torch.int64, device=device) if labels else None
+        self.tn = torch.zeros(nb, dtype=torch.int64, device=device)  # the timestep the model reads
+
+    def _body(self):  # what is captured
+        self._step()
+
+    def _advance(self):  # one denoising move
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._step()
 
     def _step(self):
         ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
@@ -422,19 +460,20 @@ class _Loop:
         if not self.m._plans or len(self.keys) != len(self.m._plans):
             self.keys = ()
             self.z.zero_()
-            self._step()  # first pass at this shape: creates the conv plans, every conv packs its own weights
+            self._body()  # first pass at this shape: creates the conv plans, every conv packs its own weights
         self.keys = self.m.pack_all()  # current weights, one launch
         if use_graph and self.graph is None and len(steps) > 2:
             s = torch.cuda.Stream()
             s.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(s):
                 self.z.zero_()
-                self._step()  # workspaces (hipMalloc) outside the capture
+                self._body()  # workspaces (hipMalloc) outside the capture
             torch.cuda.current_stream().wait_stream(s)
             torch.cuda.synchronize()
             self.graph = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):
-                self._step()
+                self._body()
+            self.captures += 1
             self._pinned = (dict(self.m._plans), dict(ops._ws_cache), self.arena)  # keep what the graph points at alive
         self._load(keep)
         self._walk(moves, steps, rows, noise, eta, reverse, on_step)
@@ -457,12 +496,109 @@ class _Loop:
             if self.inpaint:
                 noise.zk(self.zk, done)
             done += 1
+            self._advance()
+            if on_step is not None:
+                on_step(i, t, self.x)
+
+
+class _TiledLoop(_Loop):
+    """The loop of a whole case under a patch-trained model (module docstring, "Tiled sampling"): x, z, acc and wsum have the case's
+    extent, the model's buffers that of one window batch.  One captured gather -> U-Net -> accumulate body is replayed per window
+    batch after that batch's table rows, labels and context were copied (device to device) into the buffers it reads; the update
+    launch follows the last batch."""
+
+    def __init__(self, model, scheduler, shape, device, window, cond_channels=0, context_shape=None, guided=False, labels=False):
+        from . import sliding  # here, not at the top: the trainers import this module and tile nothing
+        sp = tuple(int(s) for s in shape[2:])
+        plan = window.plan(sp)
+        if plan.padded != sp:
+            raise ValueError(f"window_inferer: the case {sp} is smaller than the window {plan.roi}: a noise sample has no border to pad")
+        self.plan, self.b = plan, window.sw_batch_size
+        self.roi3 = sliding._dims3(plan.roi)
+        self.tokens = None if context_shape is None else int(context_shape[0])
+        super().__init__(model, scheduler, shape, device, cond_channels, context_shape, guided, labels)
+        n = self.n
+        self.imp = window._importance(plan.roi, torch.device(device))(plan.roi)
+        self.acc = torch.zeros(shape, dtype=F32, device=device)
+        self.wsum = torch.zeros(sp, dtype=F32, device=device)
+        self.cond = torch.empty((n, self.cc) + sp, dtype=F32, device=device) if self.cc else None  # the concat condition of the whole case
+        # the window table of every batch (row 0: N, D, H, W of the case), staged once; `table` is the one the kernels read
+        rows = sliding._rows3(plan.rows(n, self.b), len(sp))
+        self.calls = rows.shape[0]
+        head = np.asarray([n] + list(sliding._dims3(sp)), np.int32)
+        host = np.concatenate([np.broadcast_to(head, (self.calls, 1, 4)), rows], axis=1)
+        self.host_tables = torch.from_numpy(np.ascontiguousarray(host))
+        self.tables = self.host_tables.to(device)
+        self.table = self.tables[0].clone()
+        # the image every row belongs to (fillers: image 0, masked out): labels and context rows are staged per batch with it
+        image = torch.from_numpy(rows[..., 0].astype(np.int64))
+        self.row_valid = (image >= 0).to(device)
+        self.row_image = image.clamp(min=0).to(device)
+        self.labels_all = self.ctx_all = None
+
+    def _model_buffers(self, rows, sp, device, context_shape, labels):
+        super()._model_buffers(self.b, self.plan.roi, device, context_shape, labels)
+
+    def _load(self, x):
+        self.x.copy_(x)
+        self.acc.zero_()  # the passes that created plans and workspaces accumulated into it
+
+    def _load_condition(self, conditioning, class_labels, guidance_scale, null_class):
+        """The whole-case condition, the labels and context rows of every window batch (each row's image's own; fillers and the null
+        half: zeros / `null_class`), the guidance scale, and the weight sum, which does not change during a run."""
+        calls, b = self.calls, self.b
+        nb = 2 * b if self.guided else b
+        if self.cc:
+            self.cond.copy_(conditioning)
+        elif self.ctx is not None:
+            tokens = ops.cast_bf16(conditioning.contiguous().reshape(-1, conditioning.shape[2])).reshape(self.n, self.tokens, -1)
+            self.ctx_all = torch.zeros((calls, nb, self.tokens, tokens.shape[2]), dtype=torch.bfloat16, device=self.x.device)
+            self.ctx_all[:, :b] = tokens[self.row_image] * self.row_valid[..., None, None]
+            self.ctx_all = self.ctx_all.reshape(calls, nb * self.tokens, -1)
+        if self.labels is not None:
+            self.labels_all = torch.zeros((calls, nb), dtype=torch.int64, device=self.x.device)
+            self.labels_all[:, :b] = class_labels[self.row_image] * self.row_valid
+            if self.guided:
+                self.labels_all[:, b:] = int(null_class)
+        if self.guided:
+            self.w.fill_(float(guidance_scale))
+        self.wsum.zero_()
+        for k in range(calls):
+            call("mi_sw_accumulate_cl", None, None, ptr(self.imp), ptr(self.tables[k]), self.host_tables[k].data_ptr(), b, self.c, *self.roi3,
+                 ptr(self.acc), ptr(self.wsum), self.acc.numel())
+        self._stage(0)  # the passes before the first step run on the first batch
+
+    def _stage(self, k):
+        self.table.copy_(self.tables[k])
+        if self.labels is not None:
+            self.labels.copy_(self.labels_all[k])
+        if self.ctx is not None:
+            self.ctx.copy_(self.ctx_all[k])
+
+    def _body(self):
+        """gather -> U-Net -> accumulate on the batch the static table names; no host table: the kernels guard themselves."""
+        call("mi_sw_gather_cl", ptr(self.x), self.x.numel(), self.c, ptr(self.cond), self.cond.numel() if self.cc else 0, self.cc, ptr(self.table),
+             None, self.b, int(self.guided), *self.roi3, ptr(self.x_cl))
+        ctx = E.Ctx(self.arena, self.m._plans, grad_enabled=False, prepacked=self.keys)
+        eps = self.m._run(ctx, self.x_cl, self.tn, need_dx=False, class_labels=self.labels, context=self.ctx)
+        if tuple(eps.shape) != tuple(self.x_cl.shape[:-1]) + (self.c,):
+            raise ValueError(f"the model returned {tuple(eps.shape)} for windows of {tuple(self.x_cl.shape)}: its output must have the "
+                             f"sample's {self.c} channels and the window's extent")
+        call("mi_sw_accumulate_cl", ptr(eps), ptr(self.w), ptr(self.imp), ptr(self.table), None, self.b, self.c, *self.roi3, ptr(self.acc), None,
+             self.acc.numel())
+
+    def _step(self):
+        for k in range(self.calls):
+            self._stage(k)
             if self.graph is not None:
                 self.graph.replay()
             else:
-                self._step()
-            if on_step is not None:
-                on_step(i, t, self.x)
+                self._body()
+        call("mi_sw_diffusion_step", ptr(self.x), ptr(self.acc), ptr(self.wsum), ptr(self.z), ptr(self.coef), ptr(self.t), self.n, self.c, self.v,
+             self.sch.flags, self.sch.ddim)
+
+    def _advance(self):
+        self._step()
 
 
 class DiffusionInferer:
@@ -472,10 +608,19 @@ class DiffusionInferer:
         self.scheduler = scheduler
         self._loops = {}
 
-    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False, inpaint=False):
-        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape, bool(guided), bool(labels), bool(inpaint))
+    def _loop(self, model, scheduler, shape, device, cond_channels=0, context_shape=None, guided=False, labels=False, inpaint=False,
+              window=None):
+        """window: a `sliding.SlidingWindowInferer` -> the tiled loop of a case of this shape under its windows."""
+        tiling = None
+        if window is not None:
+            per_axis = lambda v: tuple(v) if isinstance(v, (tuple, list)) else v  # noqa: E731
+            tiling = (per_axis(window.roi_size), window.sw_batch_size, per_axis(window.overlap), window.mode, per_axis(window.sigma_scale))
+        key = (id(model), id(scheduler), tuple(shape), cond_channels, context_shape, bool(guided), bool(labels), bool(inpaint), tiling)
         if key not in self._loops:
-            self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape, guided, labels, inpaint)
+            if window is None:
+                self._loops[key] = _Loop(model, scheduler, tuple(shape), device, cond_channels, context_shape, guided, labels, inpaint)
+            else:
+                self._loops[key] = _TiledLoop(model, scheduler, tuple(shape), device, window, cond_channels, context_shape, guided, labels)
         return self._loops[key]
 
     @staticmethod
@@ -534,21 +679,24 @@ class DiffusionInferer:
         return conditioning, cc, ctx_shape, class_labels
 
     def _run(self, image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class, noise, input_noise=None,
-             start=0, mask=None, **how):
+             start=0, mask=None, window_inferer=None, **how):
         """The one path from the arguments of sample / img2img / inpaint / invert to the loop and its run.  image: the run's shape and, at
-        start > 0 or under a (checked) mask, its content; noise: a `_Noise`; how: what `_Loop.run` takes besides."""
+        start > 0 or under a (checked) mask, its content; noise: a `_Noise`; window_inferer: None, or the windows of the tiled loop; how:
+        what `_Loop.run` takes besides."""
+        if window_inferer is not None and mask is not None:
+            raise NotImplementedError("window_inferer= is not supported by inpaint: the tiled loop has no known region")
         conditioning, cc, ctx_shape, class_labels = self._conditioning(image, diffusion_model, conditioning, mode, class_labels,
                                                                        guidance_scale, null_class)
         x = self._first_sample(image, input_noise, scheduler, start, noise.generator)
         known = None if mask is None else (image.float(), mask)
         loop = self._loop(diffusion_model, scheduler, image.shape, image.device, cc, ctx_shape, guidance_scale is not None,
-                          class_labels is not None, mask is not None)
+                          class_labels is not None, mask is not None, window_inferer)
         return loop.run(x, noise, (conditioning, class_labels, guidance_scale, null_class), known, start=start, **how)
 
     @torch.no_grad()
     def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
                mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
-               guidance_scale=None, null_class=None):
+               guidance_scale=None, null_class=None, window_inferer=None):
         """conditioning with mode="concat": fp32 NC'[D]HW, model_input = cat([image, conditioning], dim=1) at every step; with
         mode="crossattn": fp32 [N, tokens, cross_attention_dim], the model's `context` (train_ldm.py:349-365 passes neither).
         noises: optional sequence with the z of every step (tests pin them); generator: torch generator for the per-step noise.
@@ -557,7 +705,10 @@ class DiffusionInferer:
         guidance_scale: a float w selects classifier-free guidance (not part of the reference; PARITY UNPINNED): the model output of
         every step is m_uncond + w (m_cond - m_uncond), from one forward at batch 2N whose second half carries the null condition --
         zero context tokens, zero condition channels, and `null_class` (required with class_labels) as the label.  w = 1 is the
-        conditional model, w = 0 the unconditional one; the scale is a device scalar, so all scales share one captured graph."""
+        conditional model, w = 0 the unconditional one; the scale is a device scalar, so all scales share one captured graph.
+        window_inferer: a `sliding.SlidingWindowInferer` selects tiled sampling (module docstring; not part of the reference; PARITY
+        UNPINNED) for a case larger than the model's training patch: its roi_size, sw_batch_size, overlap, mode and sigma_scale are
+        used (its padding settings are not: a case smaller than the roi on any axis is a ValueError).  None: the plain loop."""
         inter = []
 
         def on_step(i, t, x):
@@ -565,7 +716,7 @@ class DiffusionInferer:
                 inter.append(x.clone())
 
         image = self._run(input_noise, diffusion_model, scheduler or self.scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
-                          _Noise(noises, generator), input_noise, use_graph=use_graph, on_step=on_step, eta=eta)
+                          _Noise(noises, generator), input_noise, window_inferer=window_inferer, use_graph=use_graph, on_step=on_step, eta=eta)
         return (image, inter) if save_intermediates else image
 
     @staticmethod
@@ -602,7 +753,8 @@ class DiffusionInferer:
 
     @torch.no_grad()
     def img2img(self, image, diffusion_model, strength, input_noise=None, scheduler=None, conditioning=None, mode="crossattn", verbose=True,
-                noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None, guidance_scale=None, null_class=None):
+                noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None, guidance_scale=None, null_class=None,
+                window_inferer=None):
         """Partial-noise start (SDEdit's `strength`; the noise-and-reconstruct recipe of anomaly maps; not part of the reference: PARITY
         UNPINNED): the last n_run = min(int(n strength), n) of the scheduler's n steps, from scheduler.add_noise(image, input_noise,
         timesteps[n - n_run]) -- or from input_noise itself when all n run: strength 1 is `sample(input_noise)`.  The loop, kernels and
@@ -610,12 +762,12 @@ class DiffusionInferer:
         scheduler = scheduler or self.scheduler
         start = self._start(scheduler, strength)
         return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
-                         _Noise(noises, generator), input_noise, start, use_graph=use_graph, eta=eta)
+                         _Noise(noises, generator), input_noise, start, window_inferer=window_inferer, use_graph=use_graph, eta=eta)
 
     @torch.no_grad()
     def inpaint(self, image, mask, diffusion_model, strength=1.0, input_noise=None, known_noise=None, known_noises=None, resample=None,
                 scheduler=None, conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0,
-                class_labels=None, guidance_scale=None, null_class=None, on_step=None):
+                class_labels=None, guidance_scale=None, null_class=None, on_step=None, window_inferer=None):
         """Regenerate the region where mask is 1 so that it agrees with the image kept where mask is 0 (in the manner of RePaint, Lugmayr
         et al. 2022; not part of the reference: PARITY UNPINNED).  mask: bool or float [N, 1, *spatial] or [1, 1, *spatial]; values
         between 0 and 1 blend (a feathered edge).  After every step the kept region is the image at the level the step arrived at,
@@ -627,7 +779,8 @@ class DiffusionInferer:
         known_noises pins zk: one tensor, or one per denoising move.
         resample=(jump_length, jump_n_sample): `resample_moves` -- without it the region does not harmonise with its surroundings when
         the model was not trained for inpainting.  noises: one z per move of either kind, in move order.
-        on_step(i, t, x): called after every denoising move.  The other arguments as `sample`."""
+        on_step(i, t, x): called after every denoising move.  The other arguments as `sample`, except window_inferer: tiled sampling
+        has no known region (NotImplementedError)."""
         scheduler = scheduler or self.scheduler
         self._check_mask(mask, image.shape)
         start = self._start(scheduler, strength)
@@ -636,21 +789,22 @@ class DiffusionInferer:
         moves = None if resample is None else resample_moves(len(scheduler.timesteps), resample[0], resample[1], start)
         fresh = (not isinstance(scheduler, DDIMScheduler) or eta > 0) if known_noise is None else known_noise == "fresh"
         return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class,
-                         _Noise(noises, generator, known_noises, fresh), input_noise, start, mask, use_graph=use_graph, on_step=on_step,
-                         eta=eta, moves=moves)
+                         _Noise(noises, generator, known_noises, fresh), input_noise, start, mask, window_inferer, use_graph=use_graph,
+                         on_step=on_step, eta=eta, moves=moves)
 
     @torch.no_grad()
     def invert(self, image, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True, class_labels=None,
-               guidance_scale=None, null_class=None, mask=None):
+               guidance_scale=None, null_class=None, mask=None, window_inferer=None):
         """Image-to-noise DDIM inversion: DDIMScheduler.reversed_step over ascending timesteps in the fused loop of `sample` (same
         captured graph, the reverse rows in its table).  Returns the noise-side sample, fp32.  PARITY UNPINNED, as the scheduler.
-        class_labels, guidance_scale, null_class: as in `sample`.  mask: refused -- there is no inversion of a masked region."""
+        class_labels, guidance_scale, null_class, window_inferer: as in `sample`.  mask: refused -- there is no inversion of a masked
+        region."""
         self._refuse_mask(mask)
         scheduler = scheduler or self.scheduler
         if not isinstance(scheduler, DDIMScheduler):
             raise TypeError(f"invert needs a DDIMScheduler (reversed_step), not {type(scheduler).__name__}")
         return self._run(image, diffusion_model, scheduler, conditioning, mode, class_labels, guidance_scale, null_class, _Noise(), image,
-                         use_graph=use_graph, reverse=True)
+                         window_inferer=window_inferer, use_graph=use_graph, reverse=True)
 
 
 class LatentDiffusionInferer(DiffusionInferer):
@@ -659,7 +813,11 @@ class LatentDiffusionInferer(DiffusionInferer):
 
     `decode_inferer=` on sample / img2img / inpaint (not part of upstream): a `sliding.SlidingWindowInferer` whose roi_size is in
     latent voxels; the final decode then runs window by window (`sliding.tiled_decode`), for latents larger than the patch the
-    autoencoder was trained on.  None: the plain decode."""
+    autoencoder was trained on.  None: the plain decode.
+
+    `window_inferer=` on sample / img2img / invert: tiled sampling of the latent (DiffusionInferer.sample), its roi_size in latent
+    voxels too; with `decode_inferer=` a patch-trained pair produces a whole case end to end.  The encoding inside img2img / invert
+    is not tiled."""
 
     def __init__(self, scheduler, scale_factor=1.0):
         super().__init__(scheduler)
@@ -681,10 +839,10 @@ class LatentDiffusionInferer(DiffusionInferer):
     @torch.no_grad()
     def sample(self, input_noise, autoencoder_model, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100,
                conditioning=None, mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
-               guidance_scale=None, null_class=None, decode_inferer=None):
+               guidance_scale=None, null_class=None, decode_inferer=None, window_inferer=None):
         out = super().sample(input_noise, diffusion_model, scheduler, save_intermediates, intermediate_steps, conditioning, mode, verbose,
                              noises=noises, generator=generator, use_graph=use_graph, eta=eta, class_labels=class_labels,
-                             guidance_scale=guidance_scale, null_class=null_class)
+                             guidance_scale=guidance_scale, null_class=null_class, window_inferer=window_inferer)
         latent, inter = out if save_intermediates else (out, None)
         image = self._decode(autoencoder_model, latent, decode_inferer)
         if save_intermediates:
@@ -693,11 +851,13 @@ class LatentDiffusionInferer(DiffusionInferer):
 
     @torch.no_grad()
     def invert(self, image, autoencoder_model, diffusion_model, scheduler=None, conditioning=None, mode="crossattn", use_graph=True,
-               class_labels=None, guidance_scale=None, null_class=None, mask=None):
-        """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor)."""
+               class_labels=None, guidance_scale=None, null_class=None, mask=None, window_inferer=None):
+        """DDIM inversion of the latent: DiffusionInferer.invert(encode_stage_2_inputs(image) * scale_factor); the encoding is the
+        plain one also when the inversion is tiled (`window_inferer=`)."""
         self._refuse_mask(mask)
         latent = autoencoder_model.encode_stage_2_inputs(image) * self.scale_factor
-        return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class)
+        return super().invert(latent, diffusion_model, scheduler, conditioning, mode, use_graph, class_labels, guidance_scale, null_class,
+                              window_inferer=window_inferer)
 
     @torch.no_grad()
     def img2img(self, image, autoencoder_model, diffusion_model, strength, input_noise=None, decode_inferer=None, **kwargs):
