@@ -398,6 +398,44 @@ int mi_ssim_pool2(const float* x, float* y, int64_t NC, int D, int H, int W, int
 int mi_ssim_finalize(const double* partials, int P, int part_stride, int S, const int* host_tiles, const double* host_counts,
                      const double* host_weights, float* ms_out, float* ssim_out, hipStream_t stream);
 
+/* ---- FID / MMD / KID of two sets of feature rows (train_ldm.py:32 `FIDMetric, MMDMetric`, :308-310 `fid(synth_features,
+ * real_features)`; third-party `generative.metrics` classes: PARITY UNPINNED; formulas in metrics.py, kernels in csrc/distmetrics.hip).
+ * Group 0 is z0: fp32 [n][K], group 1 is z1: fp32 [m][K], both contiguous (row pitch K); R = n + m stacks group 0 over group 1.
+ * Everything else is fp64 on the device and caller-owned.  Sums run in a fixed order (no floating-point atomics): bit-reproducible. */
+/* mean: fp64 [2][K], the column means of group 0 and of group 1 */
+int mi_dm_colmean(const float* z0, const float* z1, int n, int m, int64_t K, double* mean, hipStream_t stream);
+/* bytes of the partial-sum workspace of mi_dm_gram for R rows of K columns (0: R < 1 or K < 1) */
+int64_t mi_dm_gram_workspace_bytes(int R, int64_t K);
+/* 1 when R rows fit one 64-row panel: the grid is the K chunks alone and every input element is read from HBM once */
+int mi_dm_gram_single_pass(int R);
+/* G: fp64 [R][R] = Zc Zc^T, Zc the stacked rows minus their group's mean (mean: fp64 [2][K] from mi_dm_colmean; NULL: the raw rows).
+ * fp64 16x16x4 MFMA tiles over K chunks into workspace (mi_dm_gram_workspace_bytes), then a pass that adds the chunks in order and
+ * writes both triangles.  Ragged R and K are masked. */
+int mi_dm_gram(const float* z0, const float* z1, int n, int m, int64_t K, const double* mean, double* G, double* workspace,
+               hipStream_t stream);
+/* One-sided Jacobi singular values of the n x m block G[0:n][n:n+m].  Work matrix A: fp64 column-major [r][c'], r = max(n, m),
+ * c = min(n, m), c' = c + (c & 1) (a zero pad column when c is odd).  counters: int [mi_dm_jacobi_max_sweeps()], one per sweep. */
+int mi_dm_jacobi_max_sweeps(void);
+/* 1 when r * c' doubles fit in LDS (at most 8192): mi_dm_jacobi_sweep is then one launch of one workgroup */
+int mi_dm_jacobi_single_workgroup(int n, int m);
+/* A = the block (transposed when m > n), pad column zero; counters zeroed */
+int mi_dm_jacobi_init(const double* G, int n, int m, double* A, int* counters, hipStream_t stream);
+/* round `round` (0 .. c' - 2) of the round-robin ordering: c' / 2 disjoint column pairs, one workgroup each.  A pair rotates when
+ * |a_p . a_q| > 2^-50 |a_p| |a_q| and |a_p|^2 |a_q|^2 > 0; every rotation adds 1 to *counter */
+int mi_dm_jacobi_round(double* A, int r, int c_padded, int round, int* counter, hipStream_t stream);
+/* all c' - 1 rounds of one sweep: one launch per round, or one launch in all when mi_dm_jacobi_single_workgroup.  The caller reads
+ * *counter after the sweep and stops at the first sweep without a rotation */
+int mi_dm_jacobi_sweep(double* A, int r, int c_padded, int* counter, hipStream_t stream);
+/* sv: fp64 [c] = the column norms of A (the singular values, unsorted); *nuc = their sum */
+int mi_dm_jacobi_norms(const double* A, int r, int c, double* sv, double* nuc, hipStream_t stream);
+/* out: fp64 [4] = {score, term 1, term 2, term 3}, score = (term 1 + term 2) - term 3; n, m >= 2.
+ *   MI_DM_FID (G centred, mean, K and nuc used): |mu_0 - mu_1|^2, tr(G_00) / (n-1) + tr(G_11) / (m-1), 2 *nuc / sqrt((n-1)(m-1))
+ *   MI_DM_MMD (G of the raw rows): sum_{i != j} G_00 / (n(n-1)), sum_{i != j} G_11 / (m(m-1)), 2 sum G_01 / (nm)
+ *   MI_DM_KID: as MMD on k(g) = (gamma g + coef0)^degree, degree >= 1 */
+enum { MI_DM_FID = 0, MI_DM_MMD = 1, MI_DM_KID = 2 };
+int mi_dm_finalize(int mode, const double* G, int n, int m, const double* mean, int64_t K, const double* nuc, int degree, double gamma,
+                   double coef0, double* out, hipStream_t stream);
+
 /* ---- train-step glue: scheduler.add_noise (T-LDM:160), F.mse_loss (+backward) (T-LDM:169, T-DDPM:192) ------------------- */
 int mi_qsample(const float* x0, const float* noise, const float* sqrt_alphas_cumprod, const float* sqrt_one_minus_alphas_cumprod,
                const int64_t* timesteps, const float* cond, int cond_channels, void* out, float* velocity, int N, int C, int64_t V,

@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_LIB_PATH") or os.path.join(_HERE, "libmedimgen_hip.so")  # MI_LIB_PATH: ablation builds (csrc/Makefile `diag`)
 
-_p, _i, _l, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
+_p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
 
 # name -> argtypes (return type is int unless listed in _RET)
 _SIGS = {
@@ -110,6 +110,17 @@ _SIGS = {
     "mi_ssim_pairs": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _f, _f, _p, _i, _i, _p],
     "mi_ssim_pool2": [_p, _p, _l, _i, _i, _i, _i, _p],
     "mi_ssim_finalize": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
+    "mi_dm_colmean": [_p, _p, _i, _i, _l, _p, _p],
+    "mi_dm_gram_workspace_bytes": [_i, _l],
+    "mi_dm_gram_single_pass": [_i],
+    "mi_dm_gram": [_p, _p, _i, _i, _l, _p, _p, _p, _p],
+    "mi_dm_jacobi_max_sweeps": [],
+    "mi_dm_jacobi_single_workgroup": [_i, _i],
+    "mi_dm_jacobi_init": [_p, _i, _i, _p, _p, _p],
+    "mi_dm_jacobi_round": [_p, _i, _i, _i, _p, _p],
+    "mi_dm_jacobi_sweep": [_p, _i, _i, _p, _p],
+    "mi_dm_jacobi_norms": [_p, _i, _i, _p, _p, _p],
+    "mi_dm_finalize": [_i, _p, _i, _i, _p, _l, _p, _i, _d, _d, _p, _p],
     "mi_leaky_relu_fwd": [_p, _p, _l, _f, _p],
     "mi_leaky_relu_bwd": [_p, _p, _p, _l, _f, _p],
     "mi_ls_gan_loss": [_p, _i, _l, _f, _f, _p, _p, _f, _p],
@@ -152,9 +163,10 @@ _SIGS = {
     "mi_sw_diffusion_step": [_p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
 }
 _RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l,
-        "mi_pp_stats_workspace_bytes": _l}
+        "mi_pp_stats_workspace_bytes": _l, "mi_dm_gram_workspace_bytes": _l}
 _NOCHECK = {"mi_abi_version", "mi_pp_stats_workspace_bytes", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_conv1x1_skip_fusable", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
-            "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits"}
+            "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits",
+            "mi_dm_gram_workspace_bytes", "mi_dm_gram_single_pass", "mi_dm_jacobi_max_sweeps", "mi_dm_jacobi_single_workgroup"}
 
 _lib = None
 # Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
@@ -187,7 +199,7 @@ def load():
         for name, args in _SIGS.items():
             try:
                 fn = getattr(lib, name)
-            except AttributeError:  # entry points added without a version change (mi_sw_*, then mi_sw_*_cl / mi_sw_diffusion_step): a library built before them is stale too
+            except AttributeError:  # entry points added without a version change (mi_sw_*, then mi_sw_*_cl / mi_sw_diffusion_step, then mi_dm_*): a library built before them is stale too
                 raise RuntimeError(f"{LIB_PATH} is a stale library (it lacks {name}): rebuild it with "
                                    "`python -c 'import __graft_entry__ as g; g.build()'`") from None
             fn.argtypes = args
