@@ -1,9 +1,11 @@
 // SSIM / MS-SSIM of the LDM's validation (train_ldm.py:276-277 `MultiScaleSSIMMetric(...)` / `SSIMMetric(...)`, :315-321 the pairwise
 // loop; third-party `generative.metrics` classes: PARITY UNPINNED, see metrics.py for the restated formula).
 //   - k_ssim_pairs: one workgroup per (pair, channel, output tile of TH x TW x DC).  Per input plane: x / y window -> LDS, the five
-//     moments x, y, x^2, y^2, xy (about the tile's first voxel) filtered along W then H in LDS, then a KD-deep rolling filter along D
-//     in registers (an accumulator per pending output plane); ssim and cs are evaluated per output voxel and summed.  Only Sigma ssim
-//     and Sigma cs of the tile leave the chip (fp64, one pair of values per workgroup).  2-D images are D = 1, KD = 1.
+//     statistics mean x, mean y, var x, var y, cov xy of the weighted window merged along W then H in LDS, then along D by a KD-deep
+//     rolling merge in registers (an accumulator per pending output plane); the merge is the running-mean / running-spread update
+//     (ssim_merge), not a filter of raw moments, so flat regions have exactly zero variance at any level.  ssim and cs are evaluated
+//     per output voxel and summed.  Only Sigma ssim and Sigma cs of the tile leave the chip (fp64, one pair of values per workgroup).
+//     2-D images are D = 1, KD = 1.
 //   - k_ssim_pool2: floor 2x average pool of the spatial axes (the MS-SSIM pyramid), fp32.
 //   - k_ssim_finalize: per pair, the tile partials of every scale in a fixed order (fp64), relu / power / product, fp32 results.
 // The tiling depends on the shape and the kernel only, never on the number of pairs: results are reproducible bit for bit and a pair
@@ -38,6 +40,21 @@ __device__ __forceinline__ double block_sum_256_f64(double v, double* red) {
   return ((red[0] + red[1]) + red[2]) + red[3];
 }
 
+// One step of the weighted running mean / spread (West's update) of a window, for both images at once: a = (mean x, mean y, var x, var y,
+// cov xy) of the taps merged so far, v the same five of the incoming item (a sample: spreads 0).  gn = g / W_total, r = g / W_k,
+// c = g W_{k-1} / (W_k W_total) with W_k the sum of the taps up to this one, so a[2..4] end as the window's variances and covariance.
+// Unlike E[x^2] - E[x]^2 nothing cancels: in a flat window every difference is exactly 0 and the spreads stay exactly 0, whatever
+// the level -- with the raw moments a flat window at level v left v^2 * 1e-7 of rounding in each spread, against c2 = 9e-4 (the zero
+// background of two volumes whose tile starts inside the object: 1.4e-4 off in a whole tile's mean).
+__device__ __forceinline__ void ssim_merge(float (&a)[5], const float (&v)[5], float gn, float r, float c) {
+  const float dx = v[0] - a[0], dy = v[1] - a[1];
+  a[0] += r * dx;
+  a[1] += r * dy;
+  a[2] += gn * v[2] + c * (dx * dx);
+  a[3] += gn * v[3] + c * (dy * dy);
+  a[4] += gn * v[4] + c * (dx * dy);
+}
+
 template <int KD>
 __global__ void __launch_bounds__(kT) k_ssim_pairs(const float* __restrict__ xb, const float* __restrict__ yb, const int* __restrict__ pairs,
                                                    PairShape s, const float* __restrict__ taps, double* __restrict__ part, int part_stride,
@@ -61,18 +78,27 @@ __global__ void __launch_bounds__(kT) k_ssim_pairs(const float* __restrict__ xb,
   const float* x = xb + ((int64_t)pairs[2 * pair] * s.C + c) * V + (int64_t)h0 * s.W + w0;
   const float* y = yb + ((int64_t)pairs[2 * pair + 1] * s.C + c) * V + (int64_t)h0 * s.W + w0;
 
-  // moments about a per-tile origin (the tile's first input voxel): the variances are shift-invariant, and s_x = G*(x^2) - mu_x^2 then
-  // cancels on x - x0 instead of x (exact on constant regions; the fp32 taps do not sum to exactly 1)
-  const float x0 = x[(int64_t)d0 * s.H * s.W], y0 = y[(int64_t)d0 * s.H * s.W];
-
-  float gd[KD], gh[MAXK], gw[MAXK];
-#pragma unroll
-  for (int t = 0; t < KD; ++t) gd[t] = taps[t];
-#pragma unroll
-  for (int t = 0; t < MAXK; ++t) {
-    gh[t] = t < s.kH ? taps[KD + t] : 0.f;
-    gw[t] = t < s.kW ? taps[KD + s.kH + t] : 0.f;
+  // per axis (D, H, W) and tap: the three weights of ssim_merge (the fp32 taps do not sum to exactly 1: W_total is their own sum)
+  __shared__ float kc[3][3][MAXK];
+  if (tid < 3) {
+    const int n = tid == 0 ? KD : (tid == 1 ? s.kH : s.kW);
+    const float* g = taps + (tid == 0 ? 0 : (tid == 1 ? KD : KD + s.kH));
+    float tot = 0.f, wk = 0.f;
+    for (int t = 0; t < n; ++t) tot += g[t];
+    for (int t = 0; t < MAXK; ++t) {
+      const float gt = t < n ? g[t] : 0.f, prev = wk;
+      wk += gt;
+      kc[tid][0][t] = gt / tot;
+      kc[tid][1][t] = wk > 0.f ? gt / wk : 0.f;
+      kc[tid][2][t] = wk > 0.f ? gt * prev / (wk * tot) : 0.f;
+    }
   }
+  __syncthreads();
+  float gd[3][KD];  // slot t of the rolling D filter always takes tap KD - 1 - t
+#pragma unroll
+  for (int t = 0; t < KD; ++t)
+#pragma unroll
+    for (int m = 0; m < 3; ++m) gd[m][t] = kc[0][m][KD - 1 - t];
 
   float px[NLD], py[NLD];
   int loff[NLD], goff[NLD];
@@ -94,7 +120,7 @@ __global__ void __launch_bounds__(kT) k_ssim_pairs(const float* __restrict__ xb,
       }
   };
 
-  // per owned output column: KD pending output planes x 5 moments
+  // per owned output column: KD pending output planes x 5 statistics
   float acc[NPOS][KD][5];
 #pragma unroll
   for (int q = 0; q < NPOS; ++q)
@@ -109,35 +135,27 @@ __global__ void __launch_bounds__(kT) k_ssim_pairs(const float* __restrict__ xb,
 #pragma unroll
     for (int k = 0; k < NLD; ++k)
       if (loff[k] >= 0) {
-        sx[loff[k]] = px[k] - x0;
-        sy[loff[k]] = py[k] - y0;
+        sx[loff[k]] = px[k];
+        sy[loff[k]] = py[k];
       }
     __syncthreads();
     if (p + 1 < nplanes) load_plane(p + 1);  // in flight while this plane is filtered
-    // W pass: rows x vw outputs of the five moments
+    // W pass: rows x vw outputs of the five statistics
     for (int e = tid; e < rows * TW; e += kT) {
       const int rr = e / TW, j = e - rr * TW;
       if (j >= vw) continue;
       const float* ax = sx + rr * RW + j;
       const float* ay = sy + rr * RW + j;
-      float m0 = 0.f, m1 = 0.f, m2 = 0.f, m3 = 0.f, m4 = 0.f;
+      float m[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int t = 0; t < MAXK; ++t)
         if (t < s.kW) {
-          const float a = ax[t], b = ay[t], g = gw[t];
-          const float ga = g * a, gb = g * b;
-          m0 += ga;
-          m1 += gb;
-          m2 += ga * a;
-          m3 += gb * b;
-          m4 += ga * b;
+          const float smp[5] = {ax[t], ay[t], 0.f, 0.f, 0.f};
+          ssim_merge(m, smp, kc[2][0][t], kc[2][1][t], kc[2][2][t]);
         }
       const int o = rr * TW + j;
-      sh[0][o] = m0;
-      sh[1][o] = m1;
-      sh[2][o] = m2;
-      sh[3][o] = m3;
-      sh[4][o] = m4;
+#pragma unroll
+      for (int q = 0; q < 5; ++q) sh[q][o] = m[q];
     }
     __syncthreads();
     // H pass, then the rolling D filter
@@ -152,18 +170,14 @@ __global__ void __launch_bounds__(kT) k_ssim_pairs(const float* __restrict__ xb,
         for (int t = 0; t < MAXK; ++t)
           if (t < s.kH) {
             const int o = (i + t) * TW + j;
-#pragma unroll
-            for (int m = 0; m < 5; ++m) v[m] += gh[t] * sh[m][o];
+            const float row[5] = {sh[0][o], sh[1][o], sh[2][o], sh[3][o], sh[4][o]};
+            ssim_merge(v, row, kc[1][0][t], kc[1][1][t], kc[1][2][t]);
           }
       }
 #pragma unroll
-      for (int t = 0; t < KD; ++t)
-#pragma unroll
-        for (int m = 0; m < 5; ++m) acc[q][t][m] += gd[KD - 1 - t] * v[m];
+      for (int t = 0; t < KD; ++t) ssim_merge(acc[q][t], v, gd[0][t], gd[1][t], gd[2][t]);
       if (valid && p >= KD - 1) {  // acc[q][0] is output plane d0 + p - (KD - 1): complete
-        const float ux = acc[q][0][0], uy = acc[q][0][1];
-        const float vx = acc[q][0][2] - ux * ux, vy = acc[q][0][3] - uy * uy, cxy = acc[q][0][4] - ux * uy;
-        const float mx = ux + x0, my = uy + y0;
+        const float mx = acc[q][0][0], my = acc[q][0][1], vx = acc[q][0][2], vy = acc[q][0][3], cxy = acc[q][0][4];
         const float cs = (2.f * cxy + s.c2) / (vx + vy + s.c2);
         const float ss = ((2.f * mx * my + s.c1) / (mx * mx + my * my + s.c1)) * cs;
         sum_ss += ss;

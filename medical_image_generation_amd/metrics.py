@@ -20,7 +20,8 @@ metric conventions); its source is not part of the reference, so what follows is
 pyramid is built once, and an `SSIMMetric` that shares kernel, constants and data range with a `MultiScaleSSIMMetric` reads the
 latter's scale-0 sums.
 
-Kernels (csrc/metrics.hip): a fused pair kernel per scale (five moments filtered along W and H in LDS, along D in registers, ssim / cs
+Kernels (csrc/metrics.hip): a fused pair kernel per scale (the window's means, variances and covariance merged along W and H in LDS,
+along D in registers, by a running-mean / running-spread update in which flat regions have exactly zero variance; ssim / cs
 summed per output tile: no per-voxel map reaches HBM), the 2x average pool of the pyramid, and a per-pair finalize in fp64 in a fixed
 order.  The tiling depends only on the shape and the kernel, so results are bit for bit reproducible and `pairwise` equals the
 per-pair `__call__` exactly.  Torch only allocates (and casts non-fp32 inputs once).

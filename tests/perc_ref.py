@@ -43,3 +43,234 @@ def perceptual(mod, input, target, indices=None):
         idx = idx.to(input.device).long()
         loss = loss + lpips(mod, slices(input, axis).index_select(0, idx), slices(target, axis).index_select(0, idx)).mean()
     return loss
+
+
+# ------------------------------------------------------------------------------------ the kernels of csrc/perceptual.hip, in closed form
+# fp64 statements of what each kernel computes, with the per-element bound the GPU tests hold it to, and (model=True / `fault`) the
+# fp32 / bf16 arithmetic of a correct kernel and of subtly wrong ones (tests/test_perc_ref_cpu.py).  Volumes are channels-last
+# [N, D, H, W, channel stride]; slices are numbered n-major along `axis` (0 = D, 1 = H, 2 = W), pixel axes the two others in order.
+F64, F32, BF16 = torch.float64, torch.float32, torch.bfloat16
+U8, U9, U18, U22 = 2.0 ** -8, 2.0 ** -9, 2.0 ** -18, 2.0 ** -22
+GRID_THREADS = 8192 * 256        # grid_for's cap: more work items than this and a grid-stride loop makes a second trip
+HEAD_GROUPS = 4096 * 256         # the head's cap, in threads: / (C / 8) pixel groups per pass
+
+
+def bf16_round(t):
+    return t.to(F32).to(BF16)
+
+
+def as_slices(v, axis):
+    """[N, D, H, W, c] -> [N * L, A, B, c] (a view where the layout allows, else a copy)."""
+    n, d, h, w, c = v.shape
+    if axis == 0:
+        return v.reshape(n * d, h, w, c)
+    if axis == 1:
+        return v.permute(0, 2, 1, 3, 4).reshape(n * h, d, w, c)
+    return v.permute(0, 3, 1, 2, 4).reshape(n * w, d, h, c)
+
+
+def from_slices(s, axis, shape):
+    n, d, h, w, c = shape
+    if axis == 0:
+        return s.reshape(n, d, h, w, c)
+    if axis == 1:
+        return s.reshape(n, h, d, w, c).permute(0, 2, 1, 3, 4)
+    return s.reshape(n, w, d, h, c).permute(0, 2, 3, 1, 4)
+
+
+def _valid(idx, total):
+    idx = idx.long()
+    return idx, (idx >= 0) & (idx < total)
+
+
+def gather(x, C, axis, idx, shift, scale, model=False, fault=None):
+    """x [N, D, H, W, cs] (the first C channels count), idx [S] -> (out [S, A, B, 8], bound [S, A, B, 8]) in fp64: the scaling layer on
+    the selected slices, one channel broadcast to three, channels 3..7 zero, an index outside [0, N * L) a zero slice.
+    bound = 2^-8 |want| + 2^-22 (|v| + |shift|) / scale.  model: the kernel's fp32 arithmetic and bf16 output (returned as fp64)."""
+    sl = as_slices(x[..., :C], axis)
+    idx, ok = _valid(idx, sl.shape[0])
+    v = sl[idx.clamp(0, sl.shape[0] - 1)].to(F64)
+    if fault == "transposed" and axis == 1:  # pixel (a, b) read at (b, a): the slice's memory walked in the other order
+        v = v.transpose(1, 2).reshape(v.shape)
+    v = v.expand(-1, -1, -1, 3)
+    sh, sc = shift.to(F64).view(3), scale.to(F64).view(3)
+    out = torch.zeros(v.shape[:3] + (8,), dtype=F64)
+    bound = torch.zeros_like(out)
+    if model:
+        r = (1.0 / scale.to(F32).view(3))
+        val = bf16_round((v.to(F32) - shift.to(F32).view(3)) * r).to(F64)
+    else:
+        val = (v - sh) / sc
+    out[..., :3] = val * ok.view(-1, 1, 1, 1)
+    bound[..., :3] = (U8 * ((v - sh) / sc).abs() + U22 * (v.abs() + sh.abs()) / sc) * ok.view(-1, 1, 1, 1)
+    return out, bound
+
+
+def gather_presum(x, C, axis, idx, shift, scale):
+    """The model's value before its bf16 rounding (fp32 arithmetic, as fp64) -- held to half of the bound's fp32 term."""
+    sl = as_slices(x[..., :C], axis)
+    idx, ok = _valid(idx, sl.shape[0])
+    v = sl[idx.clamp(0, sl.shape[0] - 1)].to(F32).expand(-1, -1, -1, 3)
+    return ((v - shift.to(F32).view(3)) * (1.0 / scale.to(F32).view(3))).to(F64) * ok.view(-1, 1, 1, 1)
+
+
+def scatter_add(dx, ds, C, axis, idx, scale, model=False, fault=None):
+    """dx [N, D, H, W, cs] (the starting gradient), ds [S, A, B, 8], idx [S] unique where valid -> (new dx [..., :C] fp64, bound, touched
+    mask [N, D, H, W] bool): dx + g / scale on the selected slices, one channel summing the three contributions, an index outside the
+    axis skipped.  bound = 2^-8 |want| + 2^-22 (|dx_old| + sum_c |g_c| / scale_c)."""
+    shape = tuple(dx.shape[:4]) + (C,)
+    old = as_slices(dx[..., :C].to(F64), axis).clone()
+    idx, ok = _valid(idx, old.shape[0])
+    sel = idx[ok]
+    assert sel.unique().numel() == sel.numel(), "the kernel is a plain read-modify-write: valid indices must be unique"
+    g = ds[ok][..., :3].to(F64)
+    sc = scale.to(F64).view(3)
+    mag = (g.abs() / sc).sum(-1, keepdim=True) if C == 1 else g.abs() / sc
+    if model:
+        r = 1.0 / scale.to(F32).view(3)
+        g32, o32 = g.to(F32), old[sel].to(F32)
+        if C == 3:
+            new = o32 + g32 * r
+        elif fault == "g0_only":
+            new = o32 + g32[..., :1] * r[0]
+        else:
+            new = ((o32 + g32[..., :1] * r[0]) + g32[..., 1:2] * r[1]) + g32[..., 2:3] * r[2]
+        new = bf16_round(new).to(F64)
+    else:
+        new = old[sel] + ((g / sc).sum(-1, keepdim=True) if C == 1 else g / sc)
+    want, bound = old.clone(), torch.zeros_like(old)
+    want[sel] = new
+    exact = old[sel] + ((g / sc).sum(-1, keepdim=True) if C == 1 else g / sc)
+    bound[sel] = U8 * exact.abs() + U22 * (old[sel].abs() + mag)
+    touched = torch.zeros(old.shape[0], dtype=torch.bool)
+    touched[sel] = True
+    touched = from_slices(touched.view(-1, 1, 1, 1).expand(old.shape[:3] + (1,)), axis, shape[:4] + (1,))[..., 0]
+    return from_slices(want, axis, shape), from_slices(bound, axis, shape), touched
+
+
+def _windows(t):
+    """[N, H, W, C] -> the four corners of the whole 2x2 windows, scan order (row-major), each [N, H // 2, W // 2, C] (views)."""
+    ho, wo = t.shape[1] // 2, t.shape[2] // 2
+    v = t[:, :2 * ho, :2 * wo]
+    return [v[:, dy::2, dx::2] for dy in (0, 1) for dx in (0, 1)]
+
+
+def relu_pool_fwd(x, fault=None):
+    """x [N, H, W, C] -> (relu(x), its floor 2x2 max-pool): exact in any dtype.  An odd last row / column is rectified, not pooled."""
+    a = x.clamp_min(0)
+    if fault == "odd_row_unrectified" and x.shape[1] % 2:
+        a[:, -1] = x[:, -1]
+    q = _windows(a)
+    return a, torch.maximum(torch.maximum(q[0], q[1]), torch.maximum(q[2], q[3]))
+
+
+def relu_pool_bwd(a, dpooled, dadd, dtype=F64, fault=None):
+    """a [N, H, W, C] the rectified activation, dpooled [N, H // 2, W // 2, C] or None, dadd like a or None -> dx = (dadd + route(dpooled))
+    * (a > 0) in `dtype`; the pooled gradient of a window goes to its first maximum in row-major scan order (last: the planted fault)."""
+    dx = torch.zeros(a.shape, dtype=dtype) if dadd is None else dadd.to(dtype).clone()
+    if dpooled is not None and dpooled.numel():
+        q = _windows(a)
+        best, arg = q[0], torch.zeros(q[0].shape, dtype=torch.int8)
+        for k in (1, 2, 3):
+            up = (q[k] >= best) if fault == "last_maximum" else (q[k] > best)
+            best, arg = torch.where(up, q[k], best), torch.where(up, torch.full_like(arg, k), arg)
+        dq = _windows(dx)
+        dp = dpooled.to(dtype)
+        for k in range(4):
+            dq[k] += torch.where(arg == k, dp, torch.zeros_like(dp))
+    return torch.where(a > 0, dx, torch.zeros_like(dx))   # (a masked element is +0, never -0: the bit-equal tests compare signs too)
+
+
+def head(f0, f1, w, weight, eps=1e-10, model=False, fault=None):
+    """f0, f1 [npix, C], w [C] -> (loss, df0 [npix, C], bound [npix, C]) in fp64: the closed form of mi_lpips_head.
+        n = f / (||f|| + eps),  loss = coef sum_pixels sum_c w_c (n0_c - n1_c)^2,  coef = weight / npix
+        df0 = g / r0 - f0 t,  g_c = 2 coef w_c (n0_c - n1_c),  r0 = ||f0|| + eps,  t = <g, f0> / (r0^2 ||f0||), t = 0 where ||f0|| = 0
+    bound = 2^-8 |want| + 2^-18 (|g_c| / r0 + |f0_c| |t|).  model: fp32 arithmetic in the kernel's order, bf16 df0."""
+    dt = F32 if model else F64
+    u, v, wl = f0.to(dt), f1.to(dt), w.to(dt).view(1, -1)
+    npix = u.shape[0]
+    coef = float(torch.tensor(weight, dtype=F32)) / npix          # the kernel takes weight and eps as floats
+    if model:
+        coef = float(torch.tensor(coef, dtype=F32))
+    eps = float(torch.tensor(eps, dtype=F32))
+    nu = (u * u).sum(-1, keepdim=True).sqrt()
+    r0, r1 = nu + eps, (v * v).sum(-1, keepdim=True).sqrt() + eps
+    i0, i1 = 1.0 / r0, 1.0 / r1
+    d = u * i0 - v * i1
+    val = (wl * d * d).sum(-1)
+    g = 2.0 * coef * wl * d
+    gu = g * u
+    if fault == "dot_half_lanes":
+        gu = gu[:, : gu.shape[1] // 2]
+    dot = gu.sum(-1, keepdim=True)
+    t = torch.where(nu > 0, dot * i0 * i0 / nu.clamp_min(1e-30), torch.zeros_like(dot))
+    if fault == "no_second_term":
+        t = torch.zeros_like(t)
+    df = g * i0 - u * t
+    loss = coef * float(val.to(F64).sum())
+    bound = None
+    if not model:
+        bound = U8 * df.abs() + U18 * (g.abs() / r0 + u.abs() * t.abs())
+    else:
+        df = bf16_round(df).to(F64)
+    return loss, df, bound
+
+
+# ---- the shapes and inputs of tests/test_perc_kernels_gpu.py
+EDGE_VOLUME = (2, 5, 6, 7)
+LOOP_VOLUME = (1, 83, 160, 160)   # axis 0, every slice: 83 * 160 * 160 = 2 124 800 pixels > GRID_THREADS
+HEAD_SMALL = (3, 37)
+HEAD_CHANNELS = (64, 128, 256, 512)
+
+
+def extent(shape, axis):
+    return shape[0] * shape[1 + axis]
+
+
+def edge_indices(total, unique=False):
+    """Below and above the axis, a repeat (gather only) and an unsorted tail."""
+    return torch.tensor([3, -1, total, total - 1 if unique else 3, 1, 0, 5, 2], dtype=torch.int32)
+
+
+def loop_indices():
+    return torch.randperm(extent(LOOP_VOLUME, 0), generator=torch.Generator().manual_seed(83)).to(torch.int32)
+
+
+def volume(shape, C, seed, extra=2):
+    """bf16 [N, D, H, W, C + extra]: Gaussian payload, NaN in the extra channels of the stride."""
+    v = torch.full(tuple(shape) + (C + extra,), float("nan"), dtype=BF16)
+    v[..., :C] = torch.randn(tuple(shape) + (C,), generator=torch.Generator().manual_seed(seed)).to(BF16)
+    return v
+
+
+def slice_grads(S, a, b, seed):
+    """bf16 [S, A, B, 8] slice gradients; channels 3..7 carry values a correct scatter never reads."""
+    return torch.randn((S, a, b, 8), generator=torch.Generator().manual_seed(seed)).to(BF16)
+
+
+def pixel_axes(shape, axis):
+    n, d, h, w = shape
+    return [(h, w), (d, w), (d, h)][axis]
+
+
+def head_pixels(c, loop):
+    """One pixel group past a full pass of the capped grid (loop), or the small shape."""
+    return HEAD_GROUPS // (c // 8) + 37 if loop else HEAD_SMALL[0] * HEAD_SMALL[1]
+
+
+def head_inputs(npix, c, seed):
+    g = torch.Generator().manual_seed(seed)
+    f0 = F.relu(torch.randn((npix, c), generator=g)).to(BF16)
+    f1 = F.relu(torch.randn((npix, c), generator=g)).to(BF16)
+    f0[5].zero_()            # ||f0|| = 0: the second term of df0 is dropped
+    f0[npix - 3].zero_()     # (and one in the loop's second trip)
+    f1[7].zero_()
+    return f0, f1, torch.rand(c, generator=g) * 0.1
+
+
+def ratio(got, want, bound):
+    """Worst |got - want| / bound over every element; an element with bound 0 must be exact; NaN / inf anywhere is a miss."""
+    err = (got.to(F64) - want.to(F64)).abs()
+    r = torch.where(bound > 0, err / bound.clamp_min(1e-300), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, float("inf"))))
+    r = torch.where(torch.isfinite(r), r, torch.full_like(r, float("inf")))
+    return float(r.max()) if r.numel() else 0.0

@@ -28,18 +28,27 @@ def kernel(spatial_dims, kernel_type="gaussian", kernel_size=11, kernel_sigma=1.
     return out
 
 
-def ssim_cs_maps(x, y, ker, data_range=1.0, k1=0.01, k2=0.03):
-    x, y = x.to(F64), y.to(F64)
+def _means_and_cs(x, y, ker, data_range, k2, dtype):
+    x, y = x.to(dtype), y.to(dtype)
     c = x.shape[1]
-    w = ker.to(x.device)[None, None].expand(c, 1, *ker.shape).contiguous()
+    w = ker.to(device=x.device, dtype=dtype)[None, None].expand(c, 1, *ker.shape).contiguous()
     conv = F.conv3d if ker.dim() == 3 else F.conv2d
     f = lambda t: conv(t, w, groups=c)
     mx, my = f(x), f(y)
     sx, sy, sxy = f(x * x) - mx * mx, f(y * y) - my * my, f(x * y) - mx * my
-    c1, c2 = (k1 * data_range) ** 2, (k2 * data_range) ** 2
-    cs = (2 * sxy + c2) / (sx + sy + c2)
-    ssim = ((2 * mx * my + c1) / (mx * mx + my * my + c1)) * cs
-    return ssim, cs
+    c2 = (k2 * data_range) ** 2
+    return mx, my, (2 * sxy + c2) / (sx + sy + c2)
+
+
+def _luminance(mx, my, data_range, k1):
+    c1 = (k1 * data_range) ** 2
+    return (2 * mx * my + c1) / (mx * mx + my * my + c1)
+
+
+def ssim_cs_maps(x, y, ker, data_range=1.0, k1=0.01, k2=0.03, dtype=F64):
+    """The ssim and cs maps; dtype=torch.float32 is the plain fp32 restatement the per-tile bound is derived from."""
+    mx, my, cs = _means_and_cs(x, y, ker, data_range, k2, dtype)
+    return _luminance(mx, my, data_range, k1) * cs, cs
 
 
 def ssim(x, y, spatial_dims, data_range=1.0, kernel_type="gaussian", kernel_size=11, kernel_sigma=1.5, k1=0.01, k2=0.03):
@@ -63,3 +72,230 @@ def ms_ssim(x, y, spatial_dims, data_range=1.0, kernel_type="gaussian", kernel_s
     ms = torch.stack(ms)
     w = torch.tensor(weights, dtype=F64, device=ms.device).view(-1, 1)
     return torch.prod(ms ** w, dim=0)[:, None]
+
+
+# --------------------------------------------------------------------------------------------- the kernels of csrc/metrics.hip, restated
+# k_ssim_pairs' tiling, from its launch code (mi_ssim_pairs / mi_ssim_tiles): output tiles of TH x TW, depth chunks of depth_chunk(kD),
+# tile order ((c * nd + td) * nh + th) * nw + tw.  The GPU tests assert the restated tile count against mi_ssim_tiles.
+TH, TW = 16, 32
+MAX_SCALES = 8
+POOL_GRID = 8192 * 256   # threads of k_ssim_pool2's capped grid: more outputs than this and its loop makes a second trip
+F32 = torch.float32
+
+# Per-tile bound on |sum_got - sum_want| / count, for ssim and for cs: 4 x the worst per-tile-mean error of the plain fp32 torch
+# restatement (ssim_cs_maps(dtype=float32), a dense conv) against fp64 over exactly PAIR_CASES x FAMILIES x data ranges, capped at the
+# project's whole-volume tolerance (tests/test_metrics_gpu.py: TOL).  tests/test_ssim_ref_cpu.py computes it (tile_bound()) and asserts
+# this constant equals it.  The worst per family, as that test finds them:
+#   ell 1.1e-6   noise 2.7e-6   anti 1.5e-5   ident 1.9e-7   const 3.5e-3 (k = 11; 2.5e-4 at k = 4)
+# The `const` family sets it: s_x = G*(x^2) - mu_x^2 cancels in fp32 against c2 = 9e-4 wherever a window is flat, so 4 x 3.5e-3 is
+# above the cap and the cap is the bound.  A kernel has to avoid that cancellation to meet it.  k_ssim_pairs used to, by taking the
+# raw moments about the tile's first voxel: exact on constant inputs, but the same cancellation came back wherever a flat region
+# differed from that voxel -- the zero background shared by two ellipsoid volumes, in a tile that starts inside the object -- and the
+# `ident` family missed this bound at three shapes (1.19e-4 at (44,27,43) k11, 1.40e-4 at 2-D k11, 1.32e-4 at 2-D uniform k7; `shifted`
+# below restates that formulation).  It now merges means and spreads (ssim_merge: nothing cancels, flat windows are exact at any
+# level) and sits at 5e-7.  At 1e-4 the tightest planted fault, one voxel of a full 8192-voxel tile, still shows on a pair of
+# identical images: 1 / 8192 = 1.22e-4.
+TILE_BOUND_CAP = 1e-4
+TILE_BOUND = 1e-4
+
+
+def tile_bound(worst_plain_error):
+    return min(4.0 * worst_plain_error, TILE_BOUND_CAP)
+
+
+def dhw(spatial):
+    return (1, *spatial) if len(spatial) == 2 else tuple(spatial)
+
+
+def depth_chunk(kd):
+    return 16 if kd <= 5 else 32
+
+
+def tiling(spatial, ksize):
+    """((Do, Ho, Wo), DC, (nd, nh, nw)) of a (D, H, W) volume under a (kD, kH, kW) kernel."""
+    out = tuple(e - k + 1 for e, k in zip(spatial, ksize))
+    dc = depth_chunk(ksize[0])
+    return out, dc, (-(-out[0] // dc), -(-out[1] // TH), -(-out[2] // TW))
+
+
+def tiles_per_channel(spatial, ksize):
+    n = tiling(spatial, ksize)[2]
+    return n[0] * n[1] * n[2]
+
+
+TILE_FAULTS = ("ragged_w_column", "ragged_d_plane", "chunk2_plane_twice", "other_channel", "no_origin_shift", "voxel")
+
+
+def tile_partials(x, y, ker, data_range=1.0, k1=0.01, k2=0.03, dtype=F64, fault=None, shifted=False):
+    """Per-tile sums of the ssim and cs maps of ssim_cs_maps for the image pairs (x[i], y[i]): ([P, tiles, 2] fp64 -- (sum ssim, sum cs)
+    in the kernel's tile order --, [tiles] voxel counts).  dtype=float32: the maps of the plain fp32 restatement (summed in fp64);
+    shifted: the moments are taken about each tile's first input voxel (exact on constant inputs; the kernel's formulation until it
+    took up the merge of means and spreads).  fault: one of TILE_FAULTS, planted in
+    the first tile it applies to (ValueError if there is none) -- what a subtly wrong kernel would do."""
+    sd = ker.dim()
+    ksize = dhw(tuple(ker.shape))
+    P, C = x.shape[:2]
+    spatial = dhw(tuple(x.shape[2:]))
+    (Do, Ho, Wo), dc, (nd, nh, nw) = tiling(spatial, ksize)
+    x5, y5 = x.reshape(P, C, *spatial), y.reshape(P, C, *spatial)
+    if not shifted:
+        mx, my, cs = _means_and_cs(x, y, ker, data_range, k2, dtype)
+        mx, my, cs = (t.reshape(P, C, Do, Ho, Wo) for t in (mx, my, cs))
+        ss = _luminance(mx, my, data_range, k1) * cs
+    part = torch.zeros((P, C * nd * nh * nw, 2), dtype=F64)
+    counts = torch.zeros(C * nd * nh * nw, dtype=F64)
+    planted = fault is None
+    for c in range(C):
+        for td in range(nd):
+            for th in range(nh):
+                for tw in range(nw):
+                    t = ((c * nd + td) * nh + th) * nw + tw
+                    d0, h0, w0 = td * dc, th * TH, tw * TW
+                    vd, vh, vw = min(dc, Do - d0), min(TH, Ho - h0), min(TW, Wo - w0)
+                    src = c
+                    if fault == "other_channel" and not planted and C > 1:
+                        src, planted = (c + 1) % C, True
+                    x0 = x5[:, src, d0, h0, w0].to(dtype).view(P, 1, 1, 1)
+                    y0 = y5[:, src, d0, h0, w0].to(dtype).view(P, 1, 1, 1)
+                    if shifted:  # moments of (x - x0, y - y0) over the tile's window, the shift added back into the means
+                        win = (slice(None), slice(src, src + 1), slice(d0, d0 + vd + ksize[0] - 1), slice(h0, h0 + vh + ksize[1] - 1),
+                               slice(w0, w0 + vw + ksize[2] - 1))
+                        xs, ys = x5[win].to(dtype) - x0[:, None], y5[win].to(dtype) - y0[:, None]
+                        if sd == 2:
+                            xs, ys = xs[:, :, 0], ys[:, :, 0]
+                        ux, uy, bc = (v.reshape(P, vd, vh, vw) for v in _means_and_cs(xs, ys, ker, data_range, k2, dtype))
+                        bm, bn = ux + x0, uy + y0
+                    else:
+                        sl = (slice(None), src, slice(d0, d0 + vd), slice(h0, h0 + vh), slice(w0, w0 + vw))
+                        bm, bn, bc = mx[sl], my[sl], cs[sl]
+                    if fault == "no_origin_shift" and not planted:
+                        bs, planted = _luminance(bm - x0, bn - y0, data_range, k1) * bc, True
+                    elif shifted:
+                        bs = _luminance(bm, bn, data_range, k1) * bc
+                    else:
+                        bs = ss[sl]
+                    both = torch.stack([bs, bc], -1).to(F64)           # [P, vd, vh, vw, 2]
+                    s = both.sum((1, 2, 3))
+                    if not planted:
+                        if fault == "ragged_w_column" and vw < TW:
+                            s, planted = s - both[:, :, :, vw - 1].sum((1, 2)), True
+                        elif fault == "ragged_d_plane" and vd < dc and nd > 1:
+                            s, planted = s - both[:, vd - 1].sum((1, 2)), True
+                        elif fault == "chunk2_plane_twice" and td == 1:
+                            s, planted = s + both[:, 0].sum((1, 2)), True
+                        elif fault == "voxel" and (vd, vh, vw) == (dc, TH, TW):
+                            s, planted = s - both[:, vd // 2, vh // 2, vw // 2], True
+                    part[:, t] = s
+                    counts[t] = vd * vh * vw
+    if not planted:
+        raise ValueError(f"fault {fault!r} has no tile to sit in at {tuple(x.shape)} under {tuple(ker.shape)}")
+    return part, counts
+
+
+def tile_ratios(got, want, counts, bound=None):
+    """Worst |sum_got - sum_want| / count / bound over the tiles: {"ssim": r, "cs": r}.  A NaN or inf anywhere is a miss (inf)."""
+    bound = TILE_BOUND if bound is None else bound
+    err = (got.double() - want.double()).abs() / counts.double().view(1, -1, 1) / bound
+    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
+    return {"ssim": float(err[..., 0].max()), "cs": float(err[..., 1].max())}
+
+
+# ---- the shapes and inputs of tests/test_ssim_kernels_gpu.py (and of the bound's derivation)
+PAIRS = [(2, 0), (0, 1), (2, 0), (1, 1)]      # (index into xb, index into yb): a repeat, and both orders of unequal indices
+FAMILIES = ("ell", "noise", "anti", "const", "ident")
+DERIVED_FROM = ("ell", "noise", "anti", "ident")
+# name, spatial_dims, channels, extent, metric arguments, data ranges.  The smallest extents at which each edge exists:
+PAIR_CASES = [
+    ("one_full_tile", 3, 1, (19, 19, 35), dict(kernel_size=4), (1.0,)),                       # 16 x 16 x 32 outputs: nothing ragged
+    ("ragged_c2", 3, 2, (21, 22, 37), dict(kernel_size=4), (1.0, 2.0)),                        # two tiles per axis, ragged 2 / 3 / 2, C = 2
+    ("w_one_column", 3, 1, (20, 19, 36), dict(kernel_size=4), (1.0,)),                         # the second W tile is one column wide
+    ("k11_chunks32", 3, 1, (44, 27, 43), dict(kernel_size=11), (1.0,)),                        # 32-deep chunks, window rows 26 = RH
+    ("mixed_taps", 3, 1, (37, 30, 40), dict(kernel_size=(4, 11, 7), kernel_sigma=(1.0, 2.0, 0.7)), (1.0,)),
+    ("kd1_3d", 3, 1, (3, 23, 37), dict(kernel_size=(1, 5, 3), kernel_sigma=(1.0, 1.5, 1.5)), (1.0,)),   # kD = 1 on a volume with D = 3
+    ("2d_k4", 2, 1, (61, 77), dict(kernel_size=4), (1.0,)),
+    ("2d_k11", 2, 1, (61, 77), dict(kernel_size=11), (1.0,)),
+    ("2d_uniform7", 2, 1, (61, 77), dict(kernel_type="uniform", kernel_size=7), (1.0,)),
+]
+
+
+def make_bases(family, channels, extent, data_range=1.0):
+    """xb, yb: two separate bases of 3 images each, [3, C, *extent] fp32, scaled to the data range."""
+    from oracle import synth
+    shape = (3, channels) + tuple(extent)
+    g = torch.Generator().manual_seed(1234 + len(family) + sum(extent))
+    rand = lambda: torch.rand(shape, generator=g)
+    if family == "ell":
+        xb = synth.ellipsoid_volume(1, "ssim", shape)
+        yb = (synth.ellipsoid_volume(1, "ssim", shape).roll(1, 0) + 0.2 * rand()).clamp(0, 1)   # yb[j] = xb[j - 1] + noise
+    elif family == "noise":
+        xb, yb = rand(), rand()
+    elif family == "anti":  # every (x, y) pair has correlation -1: gains and offsets of ONE noise field
+        n = torch.rand((1,) + shape[1:], generator=g)
+        a = torch.tensor([1.0, 0.8, 0.6]).view(3, *([1] * (len(shape) - 1)))
+        xb, yb = a * n + (1 - a) * 0.5, 1 - (a.flip(0) * n + 0.1)
+    elif family == "const":  # PAIRS[0] is 0.7 against 0.3
+        lv = lambda v: torch.tensor(v).view(3, *([1] * (len(shape) - 1))).expand(shape).contiguous()
+        xb, yb = lv([0.5, 0.6, 0.7]), lv([0.3, 0.4, 0.2])
+    elif family == "ident":  # PAIRS[3] = (1, 1) is an image against itself
+        xb = synth.ellipsoid_volume(2, "ssim", shape)
+        yb = xb.clone()
+    else:
+        raise ValueError(family)
+    return (xb * data_range).float().contiguous(), (yb * data_range).float().contiguous()
+
+
+def pair_inputs(xb, yb, pairs=PAIRS, swapped=False):
+    """The (x, y) batches the kernel pairs up; swapped: the planted fault of reading pairs[2p] for y and pairs[2p + 1] for x."""
+    ix, iy = [a for a, _ in pairs], [b for _, b in pairs]
+    if swapped:
+        ix, iy = iy, ix
+    return xb[ix], yb[iy]
+
+
+# ---- k_ssim_pool2
+def pool2(x, pool_d):
+    """x [NC, D, H, W] fp32 -> (the floor 2x average pool in fp64, the kernel's fixed-order fp32 statement)."""
+    nc, d, h, w = x.shape
+    do, ho, wo = (d // 2 if pool_d else d), h // 2, w // 2
+    v = x[:, :2 * do if pool_d else d, :2 * ho, :2 * wo]
+
+    def corners(t, plane):
+        t = t[:, plane::2] if pool_d else t
+        return t[:, :, 0::2, 0::2], t[:, :, 0::2, 1::2], t[:, :, 1::2, 0::2], t[:, :, 1::2, 1::2]
+
+    def fixed(t):
+        p0, p1, pw, pw1 = corners(t, 0)
+        s = (p0 + p1) + (pw + pw1)
+        if pool_d:
+            q0, q1, qw, qw1 = corners(t, 1)
+            s = s + ((q0 + q1) + (qw + qw1))
+        return s * (0.125 if pool_d else 0.25)
+
+    return fixed(v.double()), fixed(v.float())
+
+
+# ---- k_ssim_finalize
+def finalize(partials, tiles, counts, weights=None):
+    """partials [P, part_stride, 2] fp64, scale s owning the next tiles[s] slots -> (MS-SSIM [P] or None without weights, SSIM [P]),
+    fp64: per scale the mean of ssim / cs, relu, power, product; the last scale takes ssim, the others cs; a NaN comes out as NaN."""
+    partials = partials.double()
+    prod = torch.ones(partials.shape[0], dtype=F64)
+    ssim_out, off = None, 0
+    for sc, (nt, cnt) in enumerate(zip(tiles, counts)):
+        s = partials[:, off:off + nt].sum(1) / cnt
+        off += nt
+        if sc == 0:
+            ssim_out = s[:, 0].clone()
+        m = s[:, 0] if sc == len(tiles) - 1 else s[:, 1]
+        m = torch.where(m < 0, torch.zeros_like(m), m)   # (NaN < 0 is false: it stays)
+        if weights is not None:
+            prod = prod * torch.pow(m, weights[sc])
+    return (prod if weights is not None else None), ssim_out
+
+
+def within_one_ulp_f32(got, want64):
+    """got (fp32) equals want64 rounded to fp32, or one of that value's two fp32 neighbours; NaN matches NaN only."""
+    w = want64.to(F32)
+    got = got.to(F32).cpu()
+    up, dn = torch.nextafter(w, torch.full_like(w, float("inf"))), torch.nextafter(w, torch.full_like(w, -float("inf")))
+    return ((got == w) | (got == up) | (got == dn) | (torch.isnan(got) & torch.isnan(w)))

@@ -16,6 +16,8 @@ Tile 4x8x8 (2-D: 1x16x16), 32-channel chunks.  Shapes are the smallest at which 
                 forced 32-channel rows of 96; ragged last chunk / cout block (40 -> 72); one 8-channel chunk
   table-driven  Cin or Cout not a multiple of 8 (9 -> 32, 4 -> 16, 16 -> 4, 9 -> 256); the 64-channel mode 1 / 2 forms (9 -> 64 and 64 -> 9
                 at 2 x 20x32x32); mode 0 with 4 / 6 / 10 / 16 halo pieces per thread (1x1, (1,3,3), strided (2,2,1), k3 s2 at depth 2)
+  VGG plans     the (1,3,3) plans of the LPIPS stack: three slices, 8 -> 64 at 8 x 8, 256 -> 512 at 4 x 4, 512 -> 512 at 2 x 2 (one ragged
+                tile per slice; 2, 128 and 256 weight-gradient pairs in 3, 2 and 1 splits)
   1x1           streaming with 1, 2, 3, 4, 6 chunks; the NT GEMM (512 -> 256); 32 -> 4 / 4 -> 32 / 4 -> 4 (forward and data gradient on
                 different routes); V a multiple of 256 and not; the per-image column sums at V % 256 != 0 (leaves k_wgrad1x1)
   one channel   1 -> C, C -> 1 for C = 8, 64, two images, ragged tiles; the per-image column sums leave k_c1_wgrad for the tiled kernel
@@ -79,6 +81,11 @@ CASES = [
     case("2d_32to64", 1, 32, 64, (1, 17, 33), "IGEMM_M0_64", "IGEMM_M0_32", "WG2_GEN", 6, k=(1, 3, 3), p=(0, 1, 1), gauss=True),
     case("2d_3to16", 1, 3, 16, (1, 17, 33), "IGEMM_M0_32", "IGEMM_M0_32", "WG_REGS_NP3", 6, k=(1, 3, 3), p=(0, 1, 1), gauss=True),
     case("2d_n2", 2, 32, 64, (1, 16, 16), "IGEMM_M0_64", "IGEMM_M0_32", "WG2_GEN", 2, k=(1, 3, 3), p=(0, 1, 1), res=True, addrows=True),
+    # ---- the 2-D plans of the LPIPS VGG stack (perceptual.py: N = slices, (1,3,3) p (0,1,1)), from a 16 x 16 tile's 8 x 8 level down to 2 x 2:
+    # one 1 x 16 x 16 tile per slice, so ntiles = 3; pairs = (Cout / 32) x (Cin / 32): 2, 128, 256 -> pick_nsplit gives 3, 2, 1 splits
+    case("vgg_8to64", 3, 8, 64, (1, 8, 8), "IGEMM_M0_64", "IGEMM_M0_32", "WG2_GEN", 3, k=(1, 3, 3), p=(0, 1, 1)),
+    case("vgg_256to512", 3, 256, 512, (1, 4, 4), "IGEMM_M0_64", "IGEMM_M0_64", "WG2_GEN", 2, k=(1, 3, 3), p=(0, 1, 1)),
+    case("vgg_512to512", 3, 512, 512, (1, 2, 2), "IGEMM_M0_64", "IGEMM_M0_64", "WG2_GEN", 1, k=(1, 3, 3), p=(0, 1, 1), gauss=True),
     # ---- conv27 variants
     case("64to64", 1, 64, 64, (5, 9, 9), "C27_1_FWD", "C27_1_DG", "WG_ROLL", 8, gauss=True, res=True),
     case("roll_min", 1, 32, 32, (13, 9, 9), "C27_ROLL_FWD", "C27_ROLL_DG", "WG_ROLL", 16, sums=True, gauss=True, res=True),
