@@ -27,6 +27,9 @@ extern "C" {
 #define MI_ERR_BAD_ARG 10001
 #define MI_ERR_UNSUPPORTED 10002
 
+/* The one statement of the ABI version: mi_abi_version() returns it and the Python binding reads it from this file, as it reads every
+ * declaration and constant below.  Raise it when an entry point changes its argument list under an unchanged name. */
+#define MI_ABI_VERSION 20
 int mi_abi_version(void);
 
 /* ---- model boundary / layout (replaces .to(device) + autocast casts, T-LDM:144,148) ------------------------------------ */

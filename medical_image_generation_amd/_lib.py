@@ -7,203 +7,118 @@ library is `tensor.data_ptr()`.
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MI_LIB_PATH") or os.path.join(_HERE, "libmedimgen_hip.so")  # MI_LIB_PATH: ablation builds (csrc/Makefile `diag`)
 
-_p, _i, _l, _f, _d = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_double
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "medimgen_hip.h")  # the library is only built and used in-tree
 
-# name -> argtypes (return type is int unless listed in _RET)
-_SIGS = {
-    "mi_abi_version": [],
-    "mi_ncdhw_f32_to_ndhwc_bf16": [_p, _p, _i, _i, _l, _p],
-    "mi_ndhwc_bf16_to_ncdhw_f32": [_p, _p, _i, _i, _l, _p],
-    "mi_cast_f32_to_bf16": [_p, _p, _l, _p],
-    "mi_add_bf16": [_p, _p, _p, _l, _p],
-    "mi_copy_channels": [_p, _i, _i, _p, _i, _i, _i, _l, _p],
-    "mi_upsample_nearest_fwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_upsample_nearest_bwd": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_space_to_depth": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_depth_to_space": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_gn_workspace_bytes": [_i, _l, _i],
-    "mi_gn_stats": [_p, _i, _i, _l, _i, _i, _f, _p, _p, _p, _p, _p, _l, _p],
-    "mi_gn_stats_from_partial": [_p, _i, _i, _p, _i, _i, _i, _l, _i, _f, _p, _p, _p, _p, _p],
-    "mi_gn_apply": [_p, _i, _p, _p, _i, _i, _l, _i, _i, _p],
-    "mi_gn_bwd": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p, _l, _p],
-    "mi_gn_bwd_coef": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _l, _p],
-    "mi_gn_bwd_fused": [_p, _i, _p, _i, _i, _l, _i, _i, _p, _p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p, _p, _p],
-    "mi_conv_plan_create": [C.POINTER(_p), _i, _i, _i, _i, _i, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)],
-    "mi_upconv_plan_create": [C.POINTER(_p), _i, _i, _i, _i, _i, _i],
-    "mi_conv_plan_destroy": [_p],
-    "mi_conv_plan_out_dims": [_p, C.POINTER(_i)],
-    "mi_conv_pack_weights": [_p, _p, _p],
-    "mi_conv_pack_batch_create": [C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), _i],
-    "mi_conv_pack_batch_run": [_p, _p],
-    "mi_conv_pack_batch_destroy": [_p],
-    "mi_conv_fwd": [_p, _p, _i, _p, _i, _p, _i, _p, _i, _p, _p],
-    "mi_conv_fwd_stats_chunks": [_p],
-    "mi_conv_last_kernel": [],
-    "mi_conv_plan_wgrad_splits": [_p],
-    "mi_conv_dgrad": [_p, _p, _i, _p, _i, _p],
-    "mi_conv1x1_skip_fusable": [_i, _i, _l, _i, _i],
-    "mi_conv1x1_fwd_gn_apply": [_p, _p, _i, _p, _i, _p, _i, _p, _p, _i, _i, _l, _i, _i, _p],
-    "mi_conv1x1_dgrad_gn_bwd": [_p, _p, _i, _p, _i, _p, _i, _i, _l, _i, _i, _i, _p, _p, _p, _p, _i, _p, _i, _p, _p, _p, _p, _l, _p],
-    "mi_conv_wgrad": [_p, _p, _i, _p, _i, _p, _p, _i, _p],
-    "mi_linear_wgrad_bf16": [_p, _i, _i, _p, _i, _i, _l, _p, _p, _p],
-    "mi_colsum_bf16": [_p, _p, _i, _i, _l, _i, _i, _p],
-    "mi_add_f32_2d": [_p, _i, _p, _i, _i, _i, _p],
-    "mi_sum_rows_f32": [_p, _i, _i, _i, _p, _i, _p],
-    "mi_zero_f32_2d": [_p, _i, _i, _i, _p],
-    "mi_gemm_nt_bf16": [_p, _i, _l, _l, _p, _i, _l, _l, _p, _i, _l, _l, _p, _p, _i, _l, _l, _i, _i, _i, _i, _i, _f, _i, _i, _p],
-    "mi_transpose_bf16": [_p, _i, _l, _l, _p, _i, _l, _l, _i, _i, _i, _i, _p],
-    "mi_softmax_fwd": [_p, _p, _l, _i, _i, _p],
-    "mi_softmax_bwd": [_p, _p, _p, _l, _i, _i, _f, _p],
-    "mi_attn_supported": [_i, _i],
-    "mi_attn_workspace_bytes": [_i, _i, _i, _i],
-    "mi_attn_fwd": [_p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _l, _p],
-    "mi_attn_bwd": [_p, _i, _i, _i, _i, _i, _f, _p, _p, _p, _p, _p, _p, _p, _l, _p],
-    "mi_timestep_embedding": [_p, _p, _i, _i, _f, _p],
-    "mi_silu_f32": [_p, _p, _l, _p],
-    "mi_silu_bwd_f32": [_p, _p, _p, _l, _p],
-    "mi_logvar_to_sigma_fwd": [_p, _p, _l, _p],
-    "mi_logvar_to_sigma_bwd": [_p, _p, _p, _p, _l, _p],
-    "mi_embedding_add": [_p, _p, _p, _i, _i, _p],
-    "mi_embedding_bwd": [_p, _p, _p, _i, _i, _p],
-    "mi_layernorm_fwd": [_p, _i, _p, _p, _p, _i, _p, _l, _i, _f, _p],
-    "mi_layernorm_bwd": [_p, _i, _p, _i, _p, _p, _p, _i, _p, _p, _l, _i, _p],
-    "mi_geglu_fwd": [_p, _p, _l, _i, _p],
-    "mi_geglu_bwd": [_p, _p, _p, _l, _i, _p],
-    "mi_avgpool_fwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
-    "mi_avgpool_bwd": [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p],
-    "mi_crop_pad": [_p, _i, _i, _i, _i, _i, _p, _p, _i, _i, _i, _f, _i, _f, _i, _p],
-    "mi_gn_small_supported": [_i, _l, _i, _i],
-    "mi_gn_small_fwd": [_p, _i, _p, _i, _i, _l, _i, _i, _f, _p, _p, _p, _p, _i, _p],
-    "mi_aug_stats_workspace_bytes": [],
-    "mi_aug_plane_stats": [_p, _l, _p, _p, _p],
-    "mi_aug_pointwise": [_p, _l, _i, _f, _p, _p, _p, _p],
-    "mi_aug_blur_axis": [_p, _p, _i, _i, _i, _i, _p, _i, _p],
-    "mi_aug_lowres": [_p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_aug_affine_sample": [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p],
-    "mi_im2col3d": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_col2im3d": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_disc_pack_weights": [_p, _p, _p, _i, _i, _i, _i, _p],
-    "mi_disc_wgrad_unpack": [_p, _p, _i, _i, _i, _p],
-    "mi_conv2d_k4_pack": [_p, _p, _p, _i, _i, _i, _p],
-    "mi_conv2d_k4_fwd": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_conv2d_k4_dgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_conv2d_k4_wgrad_splits": [_i, _i, _i, _i, _i, _i],
-    "mi_conv2d_k4_wgrad": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_conv2d_k4_edge_fwd": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_conv2d_k4_edge_dgrad": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_conv2d_k4_edge_wgrad_splits": [_i, _i, _i, _i, _i, _i],
-    "mi_conv2d_k4_edge_wgrad": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p],
-    "mi_perc_gather": [_p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p, _p, _p, _p],
-    "mi_perc_scatter_add": [_p, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p],
-    "mi_pad_cin_f32": [_p, _p, _i, _i, _i, _i, _p],
-    "mi_relu_maxpool2_fwd": [_p, _p, _i, _i, _i, _i, _p],
-    "mi_relu_maxpool2_bwd": [_p, _p, _p, _p, _i, _i, _i, _i, _p],
-    "mi_lpips_head": [_p, _p, _p, _i, _l, _i, _f, _f, _p, _p, _p],
-    "mi_ssim_tiles": [_i, _i, _i, _i, _i, _i],
-    "mi_ssim_pairs": [_p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _i, _f, _f, _p, _i, _i, _p],
-    "mi_ssim_pool2": [_p, _p, _l, _i, _i, _i, _i, _p],
-    "mi_ssim_finalize": [_p, _i, _i, _i, _p, _p, _p, _p, _p, _p],
-    "mi_dm_colmean": [_p, _p, _i, _i, _l, _p, _p],
-    "mi_dm_gram_workspace_bytes": [_i, _l],
-    "mi_dm_gram_single_pass": [_i],
-    "mi_dm_gram": [_p, _p, _i, _i, _l, _p, _p, _p, _p],
-    "mi_dm_jacobi_max_sweeps": [],
-    "mi_dm_jacobi_single_workgroup": [_i, _i],
-    "mi_dm_jacobi_init": [_p, _i, _i, _p, _p, _p],
-    "mi_dm_jacobi_round": [_p, _i, _i, _i, _p, _p],
-    "mi_dm_jacobi_sweep": [_p, _i, _i, _p, _p],
-    "mi_dm_jacobi_norms": [_p, _i, _i, _p, _p, _p],
-    "mi_dm_finalize": [_i, _p, _i, _i, _p, _l, _p, _i, _d, _d, _p, _p],
-    "mi_leaky_relu_fwd": [_p, _p, _l, _f, _p],
-    "mi_leaky_relu_bwd": [_p, _p, _p, _l, _f, _p],
-    "mi_ls_gan_loss": [_p, _i, _l, _f, _f, _p, _p, _f, _p],
-    "mi_bn_running_update": [_p, _p, _p, _p, _i, _f, _f, _l, _p],
-    "mi_qsample": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p],
-    "mi_diffusion_step": [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _l, _i, _i, _p],
-    "mi_renoise": [_p, _p, _f, _f, _p, _i, _i, _i, _i, _l, _p],
-    "mi_qsample_drop": [_p, _p, _p, _p, _p, _p, _i, _p, _p, _i, _i, _l, _i, _p, _p],
-    "mi_select_labels": [_p, _p, _l, _p, _i, _p],
-    "mi_cast_bf16_drop": [_p, _p, _p, _i, _l, _p],
-    "mi_mse_fwd_bwd": [_p, _p, _p, _p, _i, _i, _l, _f, _p],
-    "mi_l1_fwd_bwd": [_p, _p, _p, _p, _i, _i, _l, _i, _p],
-    "mi_reparam_kl_fwd": [_p, _p, _p, _p, _p, _i, _i, _l, _f, _p],
-    "mi_reparam_kl_bwd": [_p, _p, _p, _p, _p, _p, _i, _i, _l, _f, _p],
-    "mi_sumsq_f32": [_p, _l, _p, _i, _p],
-    "mi_adam_step": [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _f, _f, _p, _p],
-    "mi_adam_step_dev": [_p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
-    "mi_adam_ema_step_dev": [_p, _p, _p, _p, _p, _l, _p, _i, _p, _f, _p, _p],
-    "mi_swap_f32": [_p, _p, _l, _p],
-    "mi_axpy_f32": [_p, _p, _f, _l, _p],
-    "mi_scale_f32": [_p, _f, _l, _p],
-    "mi_meter_bytes": [],
-    "mi_meter_reset": [_p, _p],
-    "mi_mse_eval": [_p, _p, _p, _i, _i, _l, _p],
-    "mi_l1_eval": [_p, _p, _p, _i, _i, _l, _p],
-    "mi_kl_eval": [_p, _p, _p, _i, _i, _l, _p],
-    "mi_pp_prefilter3": [_p, _p, _l, _i, _l, _p, _i, _p],
-    "mi_pp_resample_axis": [_p, _p, _l, _i, _i, _l, _p, _p, _i, _p],
-    "mi_pp_resample_labels": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p],
-    "mi_pp_nonzero_box": [_p, _i, _i, _i, _i, _p, _p],
-    "mi_pp_stats_workspace_bytes": [_i],
-    "mi_pp_box_stats": [_p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p],
-    "mi_pp_finish_image": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p, _p],
-    "mi_pp_finish_label": [_p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_sw_gather": [_p, _l, _i, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p],
-    "mi_sw_accumulate": [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p],
-    "mi_sw_finish": [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _p],
-    "mi_sw_gather_cl": [_p, _l, _i, _p, _l, _i, _p, _p, _i, _i, _i, _i, _i, _p, _p],
-    "mi_sw_accumulate_cl": [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _l, _p],
-    "mi_sw_diffusion_step": [_p, _p, _p, _p, _p, _p, _i, _i, _l, _i, _i, _p],
-}
-_RET = {"mi_gn_workspace_bytes": _l, "mi_attn_workspace_bytes": _l, "mi_aug_stats_workspace_bytes": _l, "mi_meter_bytes": _l,
-        "mi_pp_stats_workspace_bytes": _l, "mi_dm_gram_workspace_bytes": _l}
+_C_TYPES = {"int": C.c_int, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double, "hipStream_t": C.c_void_p}
+_C_RETURNS = ("int", "int64_t")
+_ENUM = re.compile(r"\benum\b\s*\w*\s*\{([^}]*)\}\s*;")
+
+
+def _parse_header(text: str):
+    """The C ABI from the header's text (no I/O): ({entry point: (restype, [argtypes])}, {MI_* macro or enumerator: int}).
+    Arguments map by ABI class -- every pointer (`*`, `T name[3]`, hipStream_t) is c_void_p -- and a declaration this does not
+    understand is an error, never an `int` by default: a wrong class resolves the symbol and then reads shifted arguments."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)  # first: the comments hold parentheses, commas and mi_*( call-like text
+    constants = {m[1]: int(m[2]) for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(MI_\w+)[ \t]+(-?\d+)[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+    for body in _ENUM.findall(text):
+        for item in filter(str.strip, body.split(",")):
+            m = re.fullmatch(r"\s*(\w+)\s*=\s*(-?\d+)\s*", item)
+            if not m:
+                raise RuntimeError(f"medimgen_hip.h: enumerator `{item.strip()}` has no explicit integer value")
+            constants[m[1]] = int(m[2])
+    functions = {}
+    for decl in re.sub(r'extern\s*"C"\s*\{|\}', " ", _ENUM.sub(" ", text)).split(";"):
+        if "(" not in decl:  # typedefs of the opaque handles
+            continue
+        decl = " ".join(decl.split())
+
+        def argtype(param):
+            words = [w for w in param.split() if w != "const"]
+            if "*" in param or param.rstrip().endswith("]"):
+                return C.c_void_p
+            if not 1 <= len(words) <= 2 or words[0] not in _C_TYPES:
+                raise RuntimeError(f"medimgen_hip.h: parameter `{param.strip()}` of `{decl};` is of no supported ABI class")
+            return _C_TYPES[words[0]]
+
+        m = re.fullmatch(r"(.*?)\s*\b(mi_\w+)\s*\(([^()]*)\)", decl)
+        if not m or m[1] not in _C_RETURNS or m[2] in functions:
+            raise RuntimeError(f"medimgen_hip.h: `{decl};` is no `int|int64_t mi_name(params);` declaration (or a second one of its name)")
+        params = [] if m[3].strip() in ("", "void") else m[3].split(",")
+        functions[m[2]] = (_C_TYPES[m[1]], [argtype(p) for p in params])
+    return functions, constants
+
+
+@functools.cache
+def _header():
+    if not os.path.exists(HEADER_PATH):
+        raise RuntimeError(f"{HEADER_PATH} is missing: the binding of libmedimgen_hip.so is derived from it")
+    with open(HEADER_PATH) as f:
+        return _parse_header(f.read())
+
+
+def constants() -> dict[str, int]:
+    """The integer `#define MI_*` macros and the enumerators of the header.  Needs no library (CPU-only hosts read them too)."""
+    return _header()[1]
+
+
+def exported_symbols() -> list[str]:
+    return sorted(_header()[0])
+
+
+def signature(name: str):
+    """(restype, argtypes) of an entry point as load() sets them."""
+    return _header()[0][name]
+
+
+# The entry points that return a value instead of a status (call_raw does not check them).
 _NOCHECK = {"mi_abi_version", "mi_pp_stats_workspace_bytes", "mi_meter_bytes", "mi_ssim_tiles", "mi_gn_small_supported", "mi_conv1x1_skip_fusable", "mi_gn_workspace_bytes", "mi_aug_stats_workspace_bytes", "mi_attn_supported", "mi_attn_workspace_bytes", "mi_conv_fwd_stats_chunks",
             "mi_conv2d_k4_wgrad_splits", "mi_conv2d_k4_edge_wgrad_splits", "mi_conv_last_kernel", "mi_conv_plan_wgrad_splits",
             "mi_dm_gram_workspace_bytes", "mi_dm_gram_single_pass", "mi_dm_jacobi_max_sweeps", "mi_dm_jacobi_single_workgroup"}
 
 _lib = None
-# Version of the C ABI this binding was written against (csrc/api.hip: mi_abi_version).  Entry points have changed their argument
-# lists under unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at
-# an old ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
-ABI_VERSION = 20
-
-
-def exported_symbols() -> list[str]:
-    return sorted(_SIGS)
+# Version of the C ABI (MI_ABI_VERSION of the header, which csrc/api.hip returns).  Entry points have changed their argument lists under
+# unchanged names between versions, and *.so files are not tracked by git: a stale library (or an MI_LIB_PATH pointing at an old
+# ablation build) resolves every symbol and then reads shifted arguments.  load() refuses it.
+ABI_VERSION = constants()["MI_ABI_VERSION"]
 
 
 def load():
-    """dlopen the library (once).  Raises RuntimeError when it has not been built."""
+    """dlopen the library (once) and bind every entry point the header declares.  Raises RuntimeError when it has not been built."""
     global _lib
     if _lib is None:
+        functions = _header()[0]
+        if _NOCHECK - set(functions):
+            raise RuntimeError(f"_lib._NOCHECK names entry points that {HEADER_PATH} does not declare: {sorted(_NOCHECK - set(functions))}")
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU / PyTorch fallback for the HIP path)")
         lib = C.CDLL(LIB_PATH)
         try:
-            lib.mi_abi_version.restype = _i
+            lib.mi_abi_version.restype = C.c_int
             have = int(lib.mi_abi_version())
         except AttributeError:
             have = None
         if have != ABI_VERSION:
             raise RuntimeError(f"{LIB_PATH} is a stale library (C ABI {have}, this binding needs {ABI_VERSION}): rebuild it with "
                                "`python -c 'import __graft_entry__ as g; g.build()'`")
-        for name, args in _SIGS.items():
+        for name, (restype, argtypes) in functions.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError:  # entry points added without a version change (mi_sw_*, then mi_sw_*_cl / mi_sw_diffusion_step, then mi_dm_*): a library built before them is stale too
                 raise RuntimeError(f"{LIB_PATH} is a stale library (it lacks {name}): rebuild it with "
                                    "`python -c 'import __graft_entry__ as g; g.build()'`") from None
-            fn.argtypes = args
-            fn.restype = _RET.get(name, _i)
+            fn.argtypes, fn.restype = argtypes, restype
         _lib = lib
     return _lib
 
@@ -216,7 +131,7 @@ class HipError(RuntimeError):
     pass
 
 
-_ERRS = {10001: "MI_ERR_BAD_ARG (host-side shape/alignment check failed)", 10002: "MI_ERR_UNSUPPORTED"}
+_ERRS = {constants()["MI_ERR_BAD_ARG"]: "MI_ERR_BAD_ARG (host-side shape/alignment check failed)", constants()["MI_ERR_UNSUPPORTED"]: "MI_ERR_UNSUPPORTED"}
 
 
 def ptr(t):

@@ -22,10 +22,11 @@ import math
 import numpy as np
 import torch
 
-from ._lib import call, call_raw, ptr
+from ._lib import call, call_raw, constants, ptr
 
 F32 = torch.float32
-SCALE, CONTRAST, GAMMA, RESTORE_STATS, ADD_NOISE, CLAMP01 = range(6)  # MI_AUG_* of include/medimgen_hip.h
+SCALE, CONTRAST, GAMMA, RESTORE_STATS, ADD_NOISE, CLAMP01 = (
+    constants()["MI_AUG_" + k] for k in ("SCALE", "CONTRAST", "GAMMA", "RESTORE_STATS", "ADD_NOISE", "CLAMP01"))
 
 
 # ------------------------------------------------------------------ scalar samplers (host; a few numbers per sample)

@@ -1,3 +1,3 @@
 #include "common.h"
 #include "medimgen_hip.h"
-extern "C" int mi_abi_version(void) { return 20; }
+extern "C" int mi_abi_version(void) { return MI_ABI_VERSION; }

@@ -219,7 +219,7 @@ def gn_apply(x, st: GNStats, silu: bool):
     return y
 
 
-GN_FUSED_REPLICAS = 16  # MI_GN_FUSED_REPLICAS of include/medimgen_hip.h
+GN_FUSED_REPLICAS = _lib.constants()["MI_GN_FUSED_REPLICAS"]
 
 
 def gn_bwd(g, x, st: GNStats, gamma, silu: bool, dgamma, dbeta, add=None, add2=None, sums=None):

@@ -60,7 +60,7 @@ from collections.abc import Sequence
 
 import torch
 
-from ._lib import call, call_raw, ptr
+from ._lib import call, call_raw, constants, ptr
 
 F32 = torch.float32
 MAX_TAPS = 11  # per axis (csrc/metrics.hip: MAXK)
@@ -325,7 +325,7 @@ def _score(bases: list[torch.Tensor], metrics: list[_SSIMBase], pairs) -> list[t
 # ------------------------------------------------------------------------------------------------------- FID / MMD / KID
 F64 = torch.float64
 MAX_JACOBI_SWEEPS = 60  # csrc/distmetrics.hip: MAX_SWEEPS; a bound, not a tuning value (8 to 14 sweeps observed)
-_DM_FID, _DM_MMD, _DM_KID = 0, 1, 2
+_DM_FID, _DM_MMD, _DM_KID = (constants()["MI_DM_" + k] for k in ("FID", "MMD", "KID"))
 
 
 def _check_features(y_pred: torch.Tensor, y: torch.Tensor):

@@ -49,10 +49,10 @@ import numpy as np
 import torch
 
 from . import hipops as ops
-from ._lib import call, ptr
+from ._lib import call, constants, ptr
 
 F32 = torch.float32
-PAD_MODES = {"constant": 0, "reflect": 1, "replicate": 2}
+PAD_MODES = {k: constants()["MI_SW_PAD_" + k.upper()] for k in ("constant", "reflect", "replicate")}
 GAUSSIAN_FLOOR = 1e-3
 
 

@@ -38,11 +38,11 @@ from . import ddp
 from . import engine as E
 from . import hipops as ops
 from . import inferer
-from ._lib import call, call_raw, ptr
+from ._lib import call, call_raw, constants, ptr
 from .optim import FusedAdam
 
 F32 = torch.float32
-METER_HEADER = 4  # include/medimgen_hip.h MI_METER_HEADER: {last batch loss, sum of batch losses, batch count, reserved}
+METER_HEADER = constants()["MI_METER_HEADER"]  # {last batch loss, sum of batch losses, batch count, reserved}
 
 
 class ValidationMeter:

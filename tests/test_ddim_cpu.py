@@ -2,15 +2,13 @@
 its docstring): timesteps, the per-step rows in both directions, the identity with the DDPM posterior that the mathematics gives,
 the tensor-level step / reversed_step, and the C-ABI surface of the fused update."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
-from tests import ddim_ref
+from tests import abi_header, ddim_ref
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN = dict(schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)  # the schedule the reference trains with (train_ldm.py:74)
 
 
@@ -136,11 +134,10 @@ def test_invert_needs_a_ddim_scheduler():
 def test_fused_update_is_declared_and_bound():
     """The entry point is in the header and the binding with one argument list (tests/test_abi_cpu.py then checks the export)."""
     from medical_image_generation_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
-    m = re.search(r"\bint mi_diffusion_step\s*\(([^)]*)\)\s*;", hdr)
-    assert m and "mi_diffusion_step" in _lib._SIGS
-    assert len(m.group(1).split(",")) == len(_lib._SIGS["mi_diffusion_step"])
-    assert _lib._SIGS["mi_diffusion_step"][-2] is ctypes.c_int  # one entry for both schedulers: the ddim selector, before the stream
+    hdr = abi_header.text()
+    assert "mi_diffusion_step" in _lib.exported_symbols()
+    assert len(abi_header.params("mi_diffusion_step")) == len(_lib.signature("mi_diffusion_step")[1])
+    assert _lib.signature("mi_diffusion_step")[1][-2] is ctypes.c_int  # one entry for both schedulers: the ddim selector, before the stream
     for old in ("mi_ddim_step", "mi_ddpm_step"):  # folded into it (ABI 20)
-        assert old not in _lib._SIGS and not re.search(r"\b%s\b" % old, hdr), old
+        assert old not in _lib.exported_symbols() and not re.search(r"\b%s\b" % old, hdr), old
     assert _lib.ABI_VERSION >= 20

@@ -1,15 +1,13 @@
 """Averaged weights, the part that needs no GPU: the two entry points are declared, bound and exported under ABI 15, refuse bad
 arguments before any launch, and FusedAdam carries the decay and the warm-up flag in the last two slots of its device block."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
 
 from oracle import cases
+from tests import abi_header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BAD_ARG = 10001
 NEW = ("mi_adam_ema_step_dev", "mi_swap_f32")
 
@@ -18,13 +16,11 @@ def test_library_exports_the_new_entry_points():
     from medical_image_generation_amd import _lib
     lib = _lib.load()
     assert _lib.ABI_VERSION >= 15 and lib.mi_abi_version() == _lib.ABI_VERSION
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
     for name in NEW:
         assert hasattr(lib, name), name
-        m = re.search(r"\bint " + name + r"\s*\(([^)]*)\)\s*;", hdr)
-        assert m and len(m.group(1).split(",")) == len(_lib._SIGS[name]), name
+        assert len(abi_header.params(name)) == len(_lib.signature(name)[1]), name
     # the shadow entry point takes mi_adam_step_dev's arguments with `ema` behind the moments
-    old, new = _lib._SIGS["mi_adam_step_dev"], _lib._SIGS["mi_adam_ema_step_dev"]
+    old, new = _lib.signature("mi_adam_step_dev")[1], _lib.signature("mi_adam_ema_step_dev")[1]
     assert new == old[:4] + [ctypes.c_void_p] + old[4:]
 
 

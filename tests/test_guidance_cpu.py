@@ -3,16 +3,15 @@ fp64 restatement (tests/guidance_ref.py) has the limits it claims, and the scale
 from a conditional-only one -- so a wrong branch order or a dropped branch cannot pass there -- with the bound those tests use
 measured here, not guessed."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
 from oracle import cases, synth
+from tests import abi_header
 from tests import guidance_ref as G
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NEW = ("mi_qsample_drop", "mi_select_labels", "mi_cast_bf16_drop")
 FOLDED = ("mi_ddpm_step_guided", "mi_ddim_step_guided")  # the guided update is mi_diffusion_step with a non-NULL guidance (ABI 20)
 
@@ -20,17 +19,15 @@ FOLDED = ("mi_ddpm_step_guided", "mi_ddim_step_guided")  # the guided update is 
 def test_library_exports_the_guidance_entry_points():
     from medical_image_generation_amd import _lib
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
+    hdr = abi_header.text()
     for name in NEW:
         assert hasattr(lib, name), name
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
+        assert len(abi_header.params(name)) == len(_lib.signature(name)[1]), name  # the binding's argument list is the header's
     for name in FOLDED:
-        assert not hasattr(lib, name) and name not in _lib._SIGS and not re.search(r"\b%s\b" % name, hdr), name
-    m = re.search(r"\bint mi_diffusion_step\s*\(([^)]*)\)\s*;", hdr)
-    assert m and "const float* guidance" in m.group(1) and len(m.group(1).split(",")) == len(_lib._SIGS["mi_diffusion_step"])
-    assert len(_lib._SIGS["mi_qsample_drop"]) == len(_lib._SIGS["mi_qsample"]) + 1
+        assert not hasattr(lib, name) and name not in _lib.exported_symbols() and not re.search(r"\b%s\b" % name, hdr), name
+    step = abi_header.params("mi_diffusion_step")
+    assert "const float* guidance" in step and len(step) == len(_lib.signature("mi_diffusion_step")[1])
+    assert len(_lib.signature("mi_qsample_drop")[1]) == len(_lib.signature("mi_qsample")[1]) + 1
 
 
 def test_combine_limits():

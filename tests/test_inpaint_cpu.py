@@ -2,16 +2,14 @@
 `mi_diffusion_step` / `mi_renoise`, the schedulers' known rows against the fp64 restatement (tests/inpaint_ref.py), the move lists of
 `resample_moves` against hand-written ones, the strength-to-start mapping, and every refusal that needs no GPU."""
 import ctypes
-import os
 import re
 
 import pytest
 import torch
 
-from tests import ddim_ref
+from tests import abi_header, ddim_ref
 from tests import inpaint_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TRAIN = dict(schedule="scaled_linear_beta", beta_start=0.0015, beta_end=0.0205)
 
 
@@ -22,17 +20,15 @@ def _list(text):
 def test_library_exports_the_inpaint_entry_points():
     from medical_image_generation_amd import _lib
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
+    hdr = abi_header.text()
     for name in ("mi_diffusion_step", "mi_renoise"):
         assert hasattr(lib, name), name
-        m = re.search(r"\bint %s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
+        assert len(abi_header.params(name)) == len(_lib.signature(name)[1]), name  # the binding's argument list is the header's
     # x, model_out, noise, table, index, guidance + mask, image, known_noise, known + x_cl, its pitch, N, C, V, flags + ddim + the stream
-    assert len(_lib._SIGS["mi_diffusion_step"]) == 6 + 4 + 6 + 1 + 1
-    assert _lib._SIGS["mi_renoise"][2:4] == [ctypes.c_float, ctypes.c_float]  # a, b by value
+    assert len(_lib.signature("mi_diffusion_step")[1]) == 6 + 4 + 6 + 1 + 1
+    assert _lib.signature("mi_renoise")[1][2:4] == [ctypes.c_float, ctypes.c_float]  # a, b by value
     for old in ("mi_ddpm_step", "mi_ddim_step", "mi_ddpm_step_guided", "mi_ddim_step_guided", "mi_step_inpaint"):  # the five it replaced
-        assert not hasattr(lib, old) and old not in _lib._SIGS and not re.search(r"\b%s\b" % old, hdr), old
+        assert not hasattr(lib, old) and old not in _lib.exported_symbols() and not re.search(r"\b%s\b" % old, hdr), old
     assert _lib.ABI_VERSION == 20 and lib.mi_abi_version() == 20
 
 

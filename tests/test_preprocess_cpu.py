@@ -9,6 +9,7 @@ import re
 import numpy as np
 import pytest
 
+from tests import abi_header
 from tests import preprocess_ref as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -149,12 +150,10 @@ def test_restatement_crop_normalise_and_class_locations():
 def test_library_exports_the_preprocess_entry_points():
     from medical_image_generation_amd import _lib
     lib = ctypes.CDLL(_lib.LIB_PATH)
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
+    hdr = abi_header.text()
     for name in ENTRY_POINTS:
         assert name in _lib.exported_symbols() and hasattr(lib, name), name
-        m = re.search(r"\b(?:int|int64_t) %s\s*\(([^)]*)\)\s*;" % name, hdr)
-        assert m, name
-        assert len(m.group(1).split(",")) == len(_lib._SIGS[name]), name  # the binding's argument list is the header's
+        assert len(abi_header.params(name)) == len(_lib.signature(name)[1]), name  # the binding's argument list is the header's
     assert "resample_image_label 1105-1167" in hdr and "configuration.py:1133-1155" in hdr  # the declarations cite the reference lines they replace
     assert _lib.ABI_VERSION == 20 and lib.mi_abi_version() == 20  # 19 with these entry points; 20: the sampler's step entries became one
     src = open(os.path.join(ROOT, "medical_image_generation_amd", "csrc", "Makefile")).read()

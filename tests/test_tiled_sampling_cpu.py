@@ -1,18 +1,15 @@
 """The fp64 restatement of tiled diffusion sampling (tests/tiled_sampling_ref.py) against what it must reduce to, and the window-plan
 facts the GPU tests (tests/test_tiled_sampling_gpu.py) rely on.  No GPU."""
-import os
-import re
 
 import pytest
 import torch
 
 from oracle import cases, step
-from tests import ddim_ref
+from tests import abi_header, ddim_ref
 from tests import sliding_ref as R
 from tests import tiled_sampling_ref as T
 
 S = cases.SEED
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _dyadic(name, shape, scale=16):
@@ -128,13 +125,11 @@ def test_binding_and_header_agree_on_the_new_entry_points():
     import ctypes
 
     from medical_image_generation_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "medimgen_hip.h")).read()
     lib = _lib.load()
     for name in ("mi_sw_gather_cl", "mi_sw_accumulate_cl", "mi_sw_diffusion_step"):
         assert name in _lib.exported_symbols() and hasattr(lib, name), name
-        m = re.search(r"\bint %s\(([^;]*)\);" % name, hdr)
-        assert m and len(m.group(1).split(",")) == len(_lib._SIGS[name]), name
-    assert _lib._SIGS["mi_sw_accumulate_cl"][1] is ctypes.c_void_p  # the guidance scale is a device pointer
+        assert len(abi_header.params(name)) == len(_lib.signature(name)[1]), name
+    assert _lib.signature("mi_sw_accumulate_cl")[1][1] is ctypes.c_void_p  # the guidance scale is a device pointer
 
 
 def test_public_surface_takes_the_keyword():
