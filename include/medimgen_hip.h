@@ -631,6 +631,63 @@ int mi_sw_gather_cl(const float* x, int64_t x_elems, int C, const float* cond, i
 int mi_sw_accumulate_cl(const void* pred, const float* guidance, const float* imp, const int* table, const int* host_table, int B, int Co, int td, int th, int tw, float* acc, float* wsum, int64_t acc_elems, hipStream_t stream);
 int mi_sw_diffusion_step(float* x, float* acc, const float* wsum, const float* noise, const float* table, const int64_t* index, int N, int C, int64_t V, int flags, int ddim, hipStream_t stream);
 
+/* ---- vector quantiser of the VQ-VAE (train_autoencoder.py:50-51, 407-409 `VQVAE(**config['vqvae_params'])` under `--latent_space_type
+ * vq`; train_ldm.py:54-58, 101-105; third-party `generative` classes VQVAE / EMAQuantizer, restated in tests/vqvae_ref.py: PARITY
+ * UNPINNED).  Tokens x: channels-last bf16 [T][x_cstride], the first D channels of every row (T = N*D*H*W latent voxels); codebook
+ * (`embedding.weight`) and EMA state fp32 [K][D] / [K], dense.  1 <= D <= 256, 1 <= K <= 8192 (MI_ERR_UNSUPPORTED beyond), T <= 2^30.
+ * fp32 arithmetic, long sums folded in fp64, no float atomics: every output is bit-identical from run to run and under graph replay.
+ * 16-byte accesses when D % 8 == 0 and pitches / pointers are aligned, a scalar path otherwise. */
+/* idx[t] (int32) = argmin_k |e_k|^2 - 2 x_t . e_k, fp32 FMA throughout; ties go to the lowest k */
+int mi_vq_assign(const void* x, int x_cstride, const float* codebook, int* idx, int64_t T, int D, int K, hipStream_t stream);
+/* q = codebook[idx[t]] (an index outside [0, K) is clamped):  zq (bf16, pitch zq_cstride) = x + (q - x), the straight-through value;
+ * diff (fp32 [T][D] dense) = q - x, what mi_vq_bwd reads;  *loss = commitment_cost * mean((q - x)^2), workgroup partials (`partials`:
+ * MI_VQ_PARTIALS doubles of scratch, 8-byte aligned) folded in a fixed order.  x == NULL: zq = bf16(q) alone (decode_samples); diff,
+ * loss and partials are not touched. */
+#define MI_VQ_PARTIALS 1024
+int mi_vq_gather_loss(const void* x, int x_cstride, const float* codebook, const int* idx, void* zq, int zq_cstride, float* diff,
+                      float* loss, double* partials, int64_t T, int D, int K, float commitment_cost, hipStream_t stream);
+/* dx (bf16) = dq + c * (x - q) from diff = q - x, c = weight[0] * scale: weight is a device scalar (the loss weight, or the incoming
+ * gradient of the loss), scale = 2 * commitment_cost / (T * D) -- one captured graph serves a changing weight */
+int mi_vq_bwd(const void* dq, int dq_cstride, const float* diff, const float* weight, float scale, void* dx, int dx_cstride, int64_t T,
+              int D, hipStream_t stream);
+/* y[i] += alpha[0] * x[i] over fp32 buffers, alpha a device scalar: loss += q_weight * quantization loss inside a captured step */
+int mi_axpy_dev_f32(float* y, const float* x, const float* alpha, int64_t n, hipStream_t stream);
+/* EMAQuantizer's training-mode update from the tokens and the indices they were given:
+ *   counts_k = #{t : idx_t = k};  ema_cluster_size = decay ema_cluster_size + (1 - decay) counts;  n = sum_k ema_cluster_size;
+ *   dw_k = sum_{t : idx_t = k} x_t;  ema_w = decay ema_w + (1 - decay) dw;  embedding = ema_w / ((ema_cluster_size + eps) / (n + K eps) n)
+ *   *perplexity = exp(-sum_k p_k log(p_k + 1e-10)), p = counts / T.
+ * Counts come from integer atomics; dw_k adds the tokens of code k in ascending token order (a stable counting sort of the token ids by
+ * code, then one workgroup per code).  Four launches.  workspace: 8-byte aligned, at least
+ *   8 + 4 * (chunks * K + 2 * K + T) bytes,  chunks = min(MI_VQ_EMA_MAX_CHUNKS, ceil(T / MI_VQ_EMA_CHUNK))   (MI_ERR_BAD_ARG below) */
+#define MI_VQ_EMA_CHUNK 1024
+#define MI_VQ_EMA_MAX_CHUNKS 256
+int mi_vq_ema_update(const void* x, int x_cstride, const int* idx, int64_t T, int D, int K, float* embedding, float* ema_cluster_size,
+                     float* ema_w, float decay, float eps, float* perplexity, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+/* fixed-order forms of mi_l1_fwd_bwd (loss overwritten, dpred the same values) and mi_sumsq_f32 (out overwritten) for the VQ train step,
+ * whose captured replay is bit-equal to the eager step: workgroup partials in fp64 (`partials`: MI_VQ_PARTIALS doubles of scratch,
+ * 8-byte aligned) folded by one workgroup, where the older entries add their workgroup sums with float atomics in arrival order */
+int mi_l1_fwd_bwd_det(const void* pred, const float* target, void* dpred, float* loss, double* partials, int N, int C, int64_t V,
+                      hipStream_t stream);
+int mi_sumsq_det_f32(const float* x, int64_t n, float* out, double* partials, hipStream_t stream);
+/* out[c] += sum over rows of x[r][c] (x bf16 [rows][x_cstride], the first C channels; out fp32 [C]) in a fixed order -- the conv bias
+ * gradients of the VQ step (mi_colsum_bf16 adds workgroup totals with float atomics).  workspace: 8-byte aligned,
+ * min(MI_VQ_COLSUM_MAX_CHUNKS, ceil(rows / MI_VQ_COLSUM_ROWS)) * C doubles */
+#define MI_VQ_COLSUM_ROWS 512
+#define MI_VQ_COLSUM_MAX_CHUNKS 1024
+int mi_colsum_det_bf16(const void* x, int x_cstride, int64_t rows, int C, float* out, double* workspace, hipStream_t stream);
+/* x[i] = ab[0] * x[i] + ab[1] in place over an fp32 buffer, {a, b} device scalars: the codebook min / max normalisation of the LDM's
+ * `vq` branch (train_ldm.py:85-96: x0 = 2 (z - min) / (max - min) - 1) and its inverse after sampling (:355-360).  fp32 in and out
+ * because the consumers take fp32 NCDHW (mi_qsample's x0, the VQVAE's quantize); one captured graph serves a refreshed range */
+int mi_affine_dev_f32(float* x, const float* ab, int64_t n, hipStream_t stream);
+/* channels-last helpers of the VQ-VAE's convs of any cubic (kernel, stride, padding), which run on mi_im2col3d / mi_col2im3d +
+ * mi_gemm_nt_bf16 like the discriminator's (vqvae.py):  y[v][c] = act(x[v][c] + bias[c]) for c < C, relu != 0: ReLU -- the bias (and
+ * activation) of a ConvTranspose, whose output is a fold of patch rows and has no GEMM epilogue;  y [nvox][Cy] (dense) = the first Cy of x's C
+ * channels, zeros from channel C on -- widens a tensor whose taps * C is no multiple of 8 in front of mi_im2col3d, narrows its
+ * gradient again.  bf16, any C and pitches. */
+int mi_bias_act_bf16(const void* x, int x_cstride, const float* bias, void* y, int y_cstride, int64_t nvox, int C, int relu,
+                     hipStream_t stream);
+int mi_fit_channels_bf16(const void* x, int x_cstride, int C, void* y, int Cy, int64_t nvox, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -891,3 +891,85 @@ class LatentDiffusionInferer(DiffusionInferer):
             m = mask.to(device=out.device, dtype=out.dtype)
             out = m * out + (1 - m) * image.to(out.dtype)
         return out
+
+
+# ------------------------------------------------------------------------------------------------ VQ latents (train_ldm.py -l vq)
+def codebook_range(autoencoder):
+    """(min, max) of a VQVAE's codebook as Python floats: ONE host read (train_ldm.py:85-96 reads them once per run)."""
+    cb = autoencoder.codebook.data
+    return float(cb.min()), float(cb.max())
+
+
+def range_forward(lo, hi):
+    """{a, b} of x0 = 2 (z - lo) / (hi - lo) - 1 = a z + b."""
+    return 2.0 / (hi - lo), -2.0 * lo / (hi - lo) - 1.0
+
+
+def range_inverse(lo, hi):
+    """{a, b} of z = (x0 + 1) / 2 * (hi - lo) + lo = a x0 + b."""
+    return (hi - lo) / 2.0, (hi + lo) / 2.0
+
+
+class VQLatentDiffusionInferer(DiffusionInferer):
+    """The inferer of train_ldm.py's `vq` branch (:68-69, 85-105, 149-152, 355-360): the diffusion model works on the VQVAE's
+    PRE-quantisation encoder output normalised to [-1, 1] by the codebook's min / max; a sample is renormalised, quantised and decoded.
+    The range is read once (`refresh_codebook_range()` re-reads it) and kept as device scalars; both affine maps are one
+    `mi_affine_dev_f32` launch.  `normalize` / `denormalize` are public so that a caller can compose the pieces by hand."""
+
+    def __init__(self, scheduler, autoencoder):
+        from .vqvae import VQVAE
+        if not isinstance(autoencoder, VQVAE):
+            raise TypeError("VQLatentDiffusionInferer takes a medical_image_generation_amd.vqvae.VQVAE (an AutoencoderKL: LatentDiffusionInferer)")
+        super().__init__(scheduler)
+        self.autoencoder = autoencoder
+        self._fwd = self._inv = None
+        self.refresh_codebook_range()
+
+    def refresh_codebook_range(self):
+        self.codebook_min, self.codebook_max = codebook_range(self.autoencoder)
+        dev = self.autoencoder.codebook.device
+        self._fwd = torch.tensor(range_forward(self.codebook_min, self.codebook_max), dtype=F32, device=dev)
+        self._inv = torch.tensor(range_inverse(self.codebook_min, self.codebook_max), dtype=F32, device=dev)
+
+    def _affine(self, x, ab):
+        if not x.is_cuda:
+            raise RuntimeError("medical_image_generation_amd runs on MI355X only (no CPU fallback)")
+        y = x.detach().to(F32).clone(memory_format=torch.contiguous_format)
+        call("mi_affine_dev_f32", ptr(y), ptr(ab.to(y.device)), y.numel())
+        return y
+
+    def normalize(self, z):
+        """2 (z - min) / (max - min) - 1 (no gradient: the encoder is frozen in the LDM loop)."""
+        return self._affine(z, self._fwd)
+
+    def denormalize(self, x):
+        """(x + 1) / 2 * (max - min) + min."""
+        return self._affine(x, self._inv)
+
+    def decode(self, latent):
+        """Renormalise, quantise (no codebook update, whatever the module's mode) and decode (train_ldm.py:355-360)."""
+        ae = self.autoencoder
+        z_cl = ops.to_channels_last(self.denormalize(latent))
+        zq = ae._quantize_cl(z_cl, update=False)[0]
+        return ae.decode(ops.to_channels_first(zq, 3))
+
+    def __call__(self, inputs, diffusion_model, noise, timesteps, condition=None, mode="crossattn"):
+        with torch.no_grad():
+            latent = self.normalize(self.autoencoder.encode_stage_2_inputs(inputs))
+        return super().__call__(inputs=latent, diffusion_model=diffusion_model, noise=noise, timesteps=timesteps, condition=condition,
+                                mode=mode)
+
+    @torch.no_grad()
+    def sample(self, input_noise, diffusion_model, scheduler=None, save_intermediates=False, intermediate_steps=100, conditioning=None,
+               mode="crossattn", verbose=True, noises=None, generator=None, use_graph=True, eta=0.0, class_labels=None,
+               guidance_scale=None, null_class=None, decode_inferer=None, window_inferer=None):
+        """DiffusionInferer.sample on the latent shape (the same captured loop; DDIM, guidance and class_labels pass through), then
+        `decode`.  Windowed sampling and windowed decoding are not built for VQ latents."""
+        if window_inferer is not None or decode_inferer is not None:
+            raise NotImplementedError("window_inferer / decode_inferer: windowed sampling and decoding are not built for VQ latents")
+        out = super().sample(input_noise, diffusion_model, scheduler, save_intermediates, intermediate_steps, conditioning, mode, verbose,
+                             noises=noises, generator=generator, use_graph=use_graph, eta=eta, class_labels=class_labels,
+                             guidance_scale=guidance_scale, null_class=null_class)
+        if save_intermediates:
+            return self.decode(out[0]), [self.decode(z) for z in out[1]]
+        return self.decode(out)

@@ -48,7 +48,14 @@ class FusedAdam(torch.optim.Optimizer):
         self._ready = True
         self.hparams = torch.zeros(8, dtype=F32, device=exp_avg.device)  # {lr, beta1, beta2, eps, weight_decay, max_norm, ema decay, ema warm-up}
         self.sumsq = torch.zeros(1, dtype=F32, device=exp_avg.device)
+        self.sumsq_partials = None  # fixed_order_norm(): fp64 [MI_VQ_PARTIALS] scratch of mi_sumsq_det_f32
         self._pushed = None
+
+    def fixed_order_norm(self):
+        """Compute the clip norm with mi_sumsq_det_f32 (workgroup partials folded in a fixed order) instead of mi_sumsq_f32 (float atomics
+        in arrival order): a captured step then equals the eager one bit for bit (VQAETrainer).  Call before capture()."""
+        from ._lib import constants
+        self.sumsq_partials = torch.empty(constants()["MI_VQ_PARTIALS"], dtype=torch.float64, device=self.exp_avg.device)
 
     def add_param_group(self, param_group):
         if self._ready:
@@ -124,7 +131,9 @@ class FusedAdam(torch.optim.Optimizer):
         device block (and moving the shadow when there is one).  Does not push."""
         a = self.arena
         n = a.n_trainable
-        if self.clip:
+        if self.clip and self.sumsq_partials is not None:
+            call("mi_sumsq_det_f32", ptr(a.grad), n, ptr(self.sumsq), ptr(self.sumsq_partials))
+        elif self.clip:
             call("mi_sumsq_f32", ptr(a.grad), n, ptr(self.sumsq), 0)
         tail = (n, ptr(self.hparams), int(self.decoupled), ptr(self.sumsq) if self.clip else None, self.grad_scale, ptr(self.step_count))
         if self.ema is None:

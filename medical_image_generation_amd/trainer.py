@@ -658,17 +658,48 @@ class LDMTrainer(DDPMTrainer):
     latent-shaped (T-LDM:159); timesteps int64 [N].  The encoder runs tape-less on the same HIP kernels inside the same hipGraph.
     `scale_factor`: 1 / std of the first batch's latents (T-LDM:110-112) -- `estimate_scale_factor` -- or given."""
 
-    def __init__(self, model, autoencoder, scale_factor: float | None = None, **kw):
+    def __init__(self, model, autoencoder, scale_factor: float | None = None, latent_space_type: str | None = None, **kw):
+        from .vqvae import VQVAE
+        is_vq = isinstance(autoencoder, VQVAE)
+        if latent_space_type is None:
+            latent_space_type = "vq" if is_vq else "vae"
+        if latent_space_type not in ("vae", "vq"):
+            raise ValueError("latent_space_type must be 'vae' or 'vq' (train_ldm.py -l)")
+        if (latent_space_type == "vq") != is_vq:
+            raise TypeError(f"latent_space_type={latent_space_type!r} with a {type(autoencoder).__name__}: 'vq' takes a VQVAE, 'vae' an AutoencoderKL")
         super().__init__(model, **kw)
         self.autoencoder = autoencoder
+        self.latent_space_type = latent_space_type
         self.ae_arena = autoencoder.arena(self.device)
         self.scale_factor = None if scale_factor is None else float(scale_factor)
+        if is_vq:  # x0 = 2 (z - min) / (max - min) - 1 = a z + b with the codebook's range (train_ldm.py:85-96); {a, b} on the device
+            self._range = torch.zeros(2, dtype=F32, device=self.device)
+            self.refresh_codebook_range()
 
     def _models(self):
         return [self.model, self.autoencoder]
 
+    def refresh_codebook_range(self):
+        """Re-read min / max of the VQVAE's codebook (one host read: call it after the codebook changed, not inside a step) into the
+        device scalars the step and its captured graph read."""
+        if self.latent_space_type != "vq":
+            raise RuntimeError("refresh_codebook_range() belongs to latent_space_type='vq'")
+        self.codebook_min, self.codebook_max = inferer.codebook_range(self.autoencoder)
+        self._range.copy_(torch.tensor(inferer.range_forward(self.codebook_min, self.codebook_max), dtype=F32))
+
     def _latents(self, images, eps):
-        """encode_stage_2_inputs (AEKL:827-830): z = z_mu + eps * z_sigma, fp32 NC[D]HW, unscaled; no tape."""
+        """'vae': encode_stage_2_inputs (AEKL:827-830): z = z_mu + eps * z_sigma, fp32 NC[D]HW, unscaled; no tape.
+        'vq' (train_ldm.py:54-58): the PRE-quantisation encoder output, no tape, no quantisation; eps must be None."""
+        if self.latent_space_type == "vq":
+            ae = self.autoencoder
+            if eps is not None:
+                raise ValueError("eps must be None with latent_space_type='vq': the VQVAE's encoder draws no noise")
+            if not images.is_cuda or images.dtype != F32 or not images.is_contiguous():
+                raise ValueError("images must be a contiguous fp32 GPU tensor")
+            if images.dim() != 5 or images.shape[1] != ae.in_channels:
+                raise ValueError(f"images must be NCDHW with {ae.in_channels} channels, got {tuple(images.shape)}")
+            ctx = E.Ctx(self.ae_arena, ae._plans, grad_enabled=False, prepacked=ae.pack_all())
+            return ops.to_channels_first(ae._run_plan(ctx, ae._enc, ops.to_channels_last(images), False), 3)
         if not (images.is_cuda and eps.is_cuda):  # (this trainer's wording; every other refusal is _encode_sample's)
             raise ValueError("images and eps must be contiguous fp32 GPU tensors")
         z = _encode_sample(self.autoencoder, self.ae_arena, images, eps, False, None, 0.0)[4]
@@ -676,12 +707,18 @@ class LDMTrainer(DDPMTrainer):
 
     @torch.no_grad()
     def estimate_scale_factor(self, images, eps):
-        """scale_factor = 1 / std(z) over the first batch (T-LDM:110-112); stored and returned."""
+        """scale_factor = 1 / std(z) over the first batch (T-LDM:110-112); stored and returned ('vae' only)."""
+        if self.latent_space_type == "vq":
+            raise RuntimeError("latent_space_type='vq' normalises by the codebook's range: there is no scale factor")
         self.scale_factor = float(1.0 / torch.std(self._latents(images, eps)))
         return self.scale_factor
 
     def _scaled_latents(self, images, eps):
         """latents_scaled = autoencoder.encode_stage_2_inputs(images) * inferer.scale_factor (T-LDM:154-157)."""
+        if self.latent_space_type == "vq":  # normalised by the codebook's range instead of a scale factor
+            z = self._latents(images, eps)
+            call("mi_affine_dev_f32", ptr(z), ptr(self._range), z.numel())
+            return z
         if self.scale_factor is None:
             raise RuntimeError("scale_factor is not set: pass it or call estimate_scale_factor(first_batch, eps) (train_ldm.py:110-112)")
         z = self._latents(images, eps)
@@ -721,6 +758,10 @@ class AETrainer(_ArenaTrainer):
     def __init__(self, model, lr=5e-5, optimizer="Adam", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
                  kl_weight=1e-7, process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, extra_loss=None, overlap=None,
                  perceptual=None, perc_weight=0.125, ema_decay=None, ema_warmup=False):
+        from .vqvae import VQVAE
+        if isinstance(model, VQVAE):
+            raise TypeError(f"{type(self).__name__} trains an AutoencoderKL (KL, perceptual and adversarial terms); a VQVAE trains on "
+                            "VQAETrainer (L1 + q_weight * quantization loss): perceptual and adversarial terms with a VQVAE are out of scope")
         super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
                          grad_accumulate_step, overlap, ema_decay, ema_warmup)
         self.kl_weight = float(kl_weight)
@@ -952,3 +993,100 @@ class AEGANTrainer(AETrainer):
             else:
                 self.d_optimizer.step(replay=self._g_d)  # discriminator forward / backward + its optimizer, block refreshed first
         return loss
+
+
+class VQAETrainer(_ArenaTrainer):
+    """The autoencoder's train step under `--latent_space_type vq` (train_autoencoder.py:407-414 with `generative`'s VQVAE):
+
+        recon, quantization_loss = VQVAE(images);  loss = L1(recon, images) + q_weight * quantization_loss  ->  backward -> clip -> Adam
+
+    step(images): images fp32 NCDHW.  The nearest-code search, the straight-through gather, the commitment loss and the EMA codebook
+    update (training mode, after the gather) run inside the step and inside its captured graph (csrc/vq.hip; no host synchronisation,
+    bit-reproducible; the L1 loss, the clip norm and the bias gradients of this step are fixed-order reductions too, so a captured step
+    equals the eager one bit for bit).  `q_weight` lives in a device scalar, so a captured graph follows a changed weight.  The codebook and its EMA
+    buffers are not in the arena: neither the optimizer nor the clip norm sees them.  `q_loss` holds the last step's quantization loss
+    (unweighted), `vqvae.quantizer.perplexity` the codebook usage.  validate() runs the eval-mode forward (no codebook update) and
+    accounts the L1 term, as AETrainer does (T-AE:447-456).  Perceptual and adversarial terms are out of scope."""
+
+    def __init__(self, model, q_weight=1.0, lr=5e-5, optimizer="Adam", weight_decay=None, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=1.0,
+                 process_group=None, bucket_mb=64, device=None, grad_accumulate_step=1, overlap=None, ema_decay=None, ema_warmup=False):
+        from .vqvae import VQVAE
+        if not isinstance(model, VQVAE):
+            raise TypeError("VQAETrainer trains a medical_image_generation_amd.vqvae.VQVAE (an AutoencoderKL trains on AETrainer)")
+        world = dist.get_world_size(process_group) if (process_group is not None or dist.is_initialized()) else 1
+        if world > 1 and model.ddp_sync:
+            raise NotImplementedError("ddp_sync=True over a process group of size > 1: the all-reduce of the codebook counts and sums is "
+                                      "not on the HIP path")
+        super().__init__(model, lr, optimizer, weight_decay, betas, eps, max_grad_norm, process_group, bucket_mb, device,
+                         grad_accumulate_step, overlap, ema_decay, ema_warmup)
+        self._q_weight = torch.full((1,), float(q_weight), dtype=F32, device=self.device)
+        self.q_loss = torch.zeros(1, dtype=F32, device=self.device)
+        # fixed-order loss and clip-norm reductions: the captured step is bit-equal to the eager one
+        self._partials = torch.empty(constants()["MI_VQ_PARTIALS"], dtype=torch.float64, device=self.device)
+        self.optimizer.fixed_order_norm()
+
+    def capture(self, images, warmup=2):
+        """The warm-up passes run the step's kernels, the EMA codebook update among them, without an optimizer step: the quantiser
+        tensors and the perplexity are put back afterwards, so capture() leaves state_dict() as it found it."""
+        q = self.model.quantizer
+        live = (q.quantizer.embedding.weight.data, q.quantizer.ema_cluster_size, q.quantizer.ema_w, q.perplexity)
+        saved = [t.clone() for t in live]
+        try:
+            super().capture(images, warmup=warmup)
+        finally:
+            torch.cuda.synchronize()
+            for t, s0 in zip(live, saved):
+                t.copy_(s0)
+
+    @property
+    def q_weight(self) -> float:
+        return float(self._q_weight)
+
+    @q_weight.setter
+    def q_weight(self, v):
+        self._q_weight.fill_(float(v))
+
+    def _check(self, images):
+        m = self.model
+        if not images.is_cuda:
+            raise RuntimeError("VQAETrainer inputs must live on the GPU")
+        if images.dtype != F32 or not images.is_contiguous():
+            raise ValueError("images must be a contiguous fp32 GPU tensor")
+        if images.dim() != 5 or images.shape[1] != m.in_channels:
+            raise ValueError(f"images must be NCDHW with {m.in_channels} channels, got {tuple(images.shape)}")
+
+    def _run(self, images, grad_enabled, update):
+        m = self.model
+        self._check(images)
+        x_cl = ops.to_channels_last(images)
+        ctx = E.Ctx(self.arena, m._plans, grad_enabled=grad_enabled, prepacked=m.pack_all())
+        z = m._run_plan(ctx, m._enc, x_cl, False)
+        zq, diff, _, _ = m._quantize_cl(z, update=update, loss=self.q_loss if grad_enabled else None)
+        if ctx.tape is not None:
+            from .vqvae import vq_bwd
+            tape = ctx.tape
+            scale = 2.0 * m.commitment_cost / z.numel()
+
+            def bwd():  # straight-through: dz = dq + q_weight * 2 cc (z - q) / numel
+                dq = tape.take(zq)
+                tape.put(z, vq_bwd(dq, diff, self._q_weight, scale))
+
+            tape.record(bwd)
+        recon = m._run_plan(ctx, m._dec, zq, True)
+        if recon.shape[-1] != images.shape[1] or recon.numel() != images.numel():
+            raise ValueError(f"the reconstruction has shape {tuple(recon.shape)} (channels-last) for images {tuple(images.shape)}")
+        return ctx, recon
+
+    def _forward(self, images):
+        ctx, recon = self._run(images, True, self.model.training)
+        self.arena.grad.zero_()  # (the forward only records)
+        drecon = torch.empty_like(recon)
+        call("mi_l1_fwd_bwd_det", ptr(recon), ptr(images), ptr(drecon), ptr(self.loss), ptr(self._partials), recon.shape[0], recon.shape[-1],
+             math.prod(images.shape[2:]))
+        call("mi_axpy_dev_f32", ptr(self.loss), ptr(self.q_loss), ptr(self._q_weight), 1)
+        return ctx.tape, recon, drecon
+
+    def _eval_forward(self, meter, images, return_recon=False):
+        _, recon = self._run(images, False, False)
+        call("mi_l1_eval", ptr(recon), ptr(images), ptr(meter.acc), recon.shape[0], recon.shape[-1], math.prod(images.shape[2:]))
+        return ops.to_channels_first(recon, 3) if return_recon else None
